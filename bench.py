@@ -11,13 +11,22 @@ global object set (weak scaling, no data-path collective).  torch.distributed
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5]
                     [--objects 1024] [--object-mib 16] [--k 4 --m 8]
                     [--mode encode|decode|bao|...] [--alloc chip|contiguous|torch]
-                    [--scatter] [--dry-run]
+                    [--scatter] [--dry-run] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds everything else: the bit-exact checks against the oracle, the CPU
+baselines, the live PMC passes, the aliased (in-place) encode, the box-ceiling
+diagnostic and the N > 1 scatter sample (the --no-* / --live-pmc / --cpu-*
+options select among them).  --dump-outputs DIR writes what the last timed
+step computed to DIR/<name>.npy (a fixed, seeded sample of a large output);
+the inputs are seeded, so two builds can be compared output for output.
 
 --gpus N with N > 1 and no WORLD_SIZE in the environment: this process
 starts the N rank processes itself (RANK/LOCAL_RANK/WORLD_SIZE,
 MASTER_ADDR=127.0.0.1) before anything touches the GPU, waits for them and
 exits with their status; under torch.distributed.run WORLD_SIZE must equal N.
-Rank 0 prints one JSON line (metric/value/unit/... + roofline + cpu_baseline).
+Rank 0 prints one JSON line (metric/value/unit/ms_per_step/... + roofline;
+with --full also the checks, cpu_baseline and the side measurements).
 """
 from __future__ import annotations
 
@@ -72,8 +81,15 @@ def parse(argv=None):
                     help="ranks (one per GPU); without WORLD_SIZE in the environment bench.py starts them itself")
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None,
                     help="BASELINE.json config preset (sets mode, k, m, objects, erase, level)")
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the checks against the oracle, the CPU baselines, the live PMC "
+                         "passes, the aliased encode, the box ceiling and the N > 1 scatter sample (a plain run "
+                         "does none of them, whatever the options that select among them say)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / "
+                         "float64; outputs above 4 Mi elements as a fixed, seeded sample of positions)")
     ap.add_argument("--objects", type=int, default=1024, help="objects per GPU")
     ap.add_argument("--object-mib", type=float, default=16.0)
     ap.add_argument("--object-bytes", type=int, default=0,
@@ -162,6 +178,12 @@ def parse(argv=None):
                          "`rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` (one pass each) before this process "
                          "touches the GPU; auto = on at N=1 for the device-resident modes with one dominant kernel")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.live_pmc = "off"
+        args.no_cpu_baseline = args.no_verify = args.no_aliased = args.no_box_ceiling = True
+        args.scatter_gib = 0.0
     if args.object_bytes:
         args.object_mib = args.object_bytes / 2**20  # exact: an integer over a power of two
     if args.config:
@@ -342,7 +364,9 @@ def live_traffic(args, argv: list, timeout_s: float = 240.0, local_rank: int | N
     steps = 2
     child = [sys.executable, str(Path(__file__).resolve())] + list(argv) + [
         "--steps", str(steps), "--warmup", "1", "--live-pmc", "off", "--no-cpu-baseline", "--no-verify",
-        "--no-verify-all", "--no-aliased", "--no-box-ceiling", "--traffic-json", "none", "--gpus", "1"]
+        "--no-verify-all", "--no-aliased", "--no-box-ceiling", "--traffic-json", "none",
+        "--dump-outputs", "",  # the last of a repeated option holds: the children write no outputs
+        "--gpus", "1"]
     tmp = Path(tempfile.mkdtemp(prefix="chip_pmc_", dir="/tmp"))
     env = child_env(local_rank)
     vals, name = {}, None
@@ -1280,6 +1304,45 @@ class Workload:
                         f"{'orc_encode_full (same injected ECIES values)' if lv & 3 else 'encode()'} on "
                         f"{threads} threads")}
 
+    def outputs(self) -> dict:
+        """What a caller of the timed path holds after the last step, by name
+        (--dump-outputs): 2-D tensors are cut to the bytes the path defines
+        (row padding and the bytes before a stream's offset are never
+        written)."""
+        import numpy as np
+        a, n = self.args, self.n
+        mode, lv = a.mode, a.level
+        so, blen = getattr(self, "soff", 0), getattr(self, "blen", 0)
+        if mode == "encode":
+            return {"shards": self.out[:, :self.m * self.C]}
+        if mode == "decode":
+            return {"objects": self.out[:, :n]}
+        if mode in ("pipeline", "bao"):
+            out = {"streams": self.out[:, so:so + blen]}
+            if mode == "bao" or lv & 4:
+                out["hashes"] = self.hashes
+            return out
+        if mode in ("pipeline-decode", "bao-decode"):
+            return {"objects": self.out[:, :n], "status": self.status}
+        if mode == "scrub-batch":  # only the damaged streams are rewritten
+            rows = torch.tensor(self.damaged, device=self.dev)
+            return {"repaired_streams": self.out[rows][:, so:so + blen], "status": np.asarray(self.scrub_status)}
+        if mode == "scrub":
+            return {"repaired_streams": np.stack([np.frombuffer(bytes(f), np.uint8) for f in self.fixed[:4]])}
+        if mode == "hasher":
+            return {"digest": np.frombuffer(self.digest, np.uint8)}
+        if mode == "file":
+            return {"output_len": np.asarray([r[1].output_len for r in self.results])}
+        if mode == "e2e":
+            out = {"streams": self.h_out[:, :min(self.olens)], "lengths": np.asarray(self.olens)}
+            if lv & 4:
+                out["hashes"] = self.h_hash
+            return out
+        if mode == "e2e-decode":
+            return {"objects": self.h_out[:, :n], "lengths": np.asarray(self.dec_len),
+                    "status": np.asarray(self.dec_status)}
+        raise SystemExit(f"--dump-outputs: no outputs defined for mode {mode}")
+
     def time_aliased(self, steps: int, warmup: int, world: int):
         """the same encode with the data shards aliased (in
         place: the input already sits in the first n bytes of each output
@@ -1382,6 +1445,32 @@ class Workload:
         else:
             ok = self.hashes[0].cpu().numpy().tobytes() == O.blake3(sample)
         return ok, sample
+
+
+DUMP_MAX_ELEMS = 1 << 22  # per array: 16 MiB of float32; a mode has at most three arrays
+
+
+def dump_outputs(outputs: dict, out_dir: str, rank: int = 0) -> None:
+    """--dump-outputs: each named output as out_dir/<name>.npy (rank r > 0:
+    <name>.rank<r>.npy).  Bytes go out as float32 and lengths / statuses as
+    float64, both exact.  An output above DUMP_MAX_ELEMS elements is sampled
+    at that many positions, drawn once from a generator seeded by SEED and
+    the output's name and sorted: the same positions in every run."""
+    import zlib
+
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, t in outputs.items():
+        t = torch.as_tensor(t)
+        rows, width = t.shape if t.dim() == 2 else (1, t.numel())
+        if rows * width > DUMP_MAX_ELEMS:
+            t = t.view(rows, width) if t.dim() == 1 else t
+            g = torch.Generator().manual_seed(SEED + zlib.crc32(name.encode()))
+            pos = torch.randint(0, rows * width, (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t[(pos // width).to(t.device), (pos % width).to(t.device)]
+        arr = t.cpu().numpy().astype(np.float32 if t.dtype == torch.uint8 else np.float64)
+        np.save(d / (f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), arr)
 
 
 def scatter_sample(rank: int, world: int, per: int, dev, group) -> dict:
@@ -1557,6 +1646,8 @@ def main():
             scatter = {"skipped": f"{world} ranks share {torch.cuda.device_count()} GPU(s); RCCL needs one GPU per rank"}
     elapsed, launch_ms = wl.time_steps(args.steps, args.warmup, world)
     max_elapsed = max_over_ranks(elapsed)
+    if args.dump_outputs and not args.dry_run:  # before anything below reuses the output buffers
+        dump_outputs(wl.outputs(), args.dump_outputs, rank)
     rank_avg_ms = gather_floats(sum(launch_ms) / len(launch_ms), world)
     rank_live = [live]
     if world > 1:

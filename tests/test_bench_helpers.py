@@ -121,3 +121,45 @@ def test_bao_data_region_len_matches_the_oracle_stream(N):
     off = enc.find(bytes([last % 251 + 1]) * 1024)
     import bench
     assert off > 0 and bench.bao_data_region_len(N) == off + 1024
+
+
+def test_plain_run_switches_the_extras_off():
+    """Without --full the parsed options leave only the timed steps: no live
+    PMC, checks, CPU baselines, aliased encode, box ceiling or scatter
+    sample; with --full they are what the other options say."""
+    import bench
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.live_pmc == "off" and a.scatter_gib == 0
+    assert a.no_cpu_baseline and a.no_verify and a.no_aliased and a.no_box_ceiling
+    f = bench.parse(["--full", "--no-aliased", "--dump-outputs", "d"])
+    assert f.full and f.live_pmc == "auto" and f.scatter_gib == 1.0 and f.dump_outputs == "d"
+    assert f.no_aliased and not (f.no_cpu_baseline or f.no_verify or f.no_box_ceiling)
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: a small output is written whole (bytes as float32,
+    lengths as float64), one above DUMP_MAX_ELEMS as DUMP_MAX_ELEMS values at
+    sorted positions that depend only on the seed and the name, read through
+    a row-sliced view as the workload hands them over."""
+    import zlib
+
+    import torch
+    import bench
+    big = torch.arange(3 * (bench.DUMP_MAX_ELEMS // 2 + 5), dtype=torch.int64).remainder(251).to(torch.uint8)
+    big = big.view(3, -1)
+    outs = {"small": big[:2, 1:9], "lengths": np.asarray([5, 1 << 40]), "big": big[:, 3:]}
+    bench.dump_outputs(outs, tmp_path / "a")
+    bench.dump_outputs({k: outs[k] for k in ("big", "small", "lengths")}, tmp_path / "b", rank=1)
+    small = np.load(tmp_path / "a" / "small.npy")
+    assert small.dtype == np.float32 and np.array_equal(small, big[:2, 1:9].numpy())
+    lengths = np.load(tmp_path / "a" / "lengths.npy")
+    assert lengths.dtype == np.float64 and lengths.tolist() == [5.0, float(1 << 40)]
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.rank1.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a, b)
+    view = big[:, 3:]
+    g = torch.Generator().manual_seed(bench.SEED + zlib.crc32(b"big"))
+    pos = torch.randint(0, view.numel(), (bench.DUMP_MAX_ELEMS,), generator=g).sort().values
+    assert np.array_equal(a, view.reshape(-1)[pos].numpy())

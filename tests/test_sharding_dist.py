@@ -98,7 +98,7 @@ def test_bench_spawns_its_own_ranks_dry_run():
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--dry-run"], capture_output=True, text=True, timeout=300, cwd=root, env=env)
+                          "--dry-run", "--full"], capture_output=True, text=True, timeout=300, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -146,8 +146,8 @@ def test_bench_cfg5_eight_ranks_dry_run():
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     out = subprocess.run([sys.executable, str(root / "bench.py"), "--config", "cfg5", "--gpus", "8", "--steps", "2",
-                          "--warmup", "1", "--dry-run"], capture_output=True, text=True, timeout=600, cwd=root,
-                         env=env)
+                          "--warmup", "1", "--dry-run", "--full"], capture_output=True, text=True, timeout=600,
+                         cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -191,3 +191,8 @@ def test_bench_every_mode_dry_run(mode):
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "config", "roofline"):
         assert key in res, key
+    # a plain run (no --full) times the steps only
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    for key in ("cpu_baseline", "cpu_baseline_all_cores", "box_ceiling", "aliased_data_shards",
+                "verified_all_objects", "scatter"):
+        assert key not in res, key

@@ -6,8 +6,8 @@ set -e -o pipefail
 O=$1; N=$2; A=$3; B=$4; shift 4
 mkdir -p $O
 for i in $(seq 1 $N); do
-  env $A timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" > $O/a_$i.json 2> $O/a_$i.err
-  env $B timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" > $O/b_$i.json 2> $O/b_$i.err
+  env $A timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" > $O/a_$i.json 2> $O/a_$i.err
+  env $B timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" > $O/b_$i.json 2> $O/b_$i.err
 done
 echo "A: $A   B: $B   args: $*"
 for f in $O/a_*.json $O/b_*.json; do
