@@ -21,6 +21,7 @@
 //! There is no CPU fallback: with no gfx950 device every compute call returns
 //! [`ChipError::NoDevice`].
 pub mod ffi;
+mod ffi_ext;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -813,6 +814,86 @@ pub fn decode_batch(format: u8, input: &DeviceRows, in_len: u64, hashes: &Device
                                    scratch.ptr, stream.0)
     })?;
     Ok(out_len)
+}
+
+fn abi_ext() -> Result<()> {
+    abi()?;
+    match unsafe { ffi_ext::chipx_abi_version() } {
+        ffi_ext::CHIPX_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// Where [`encode_ragged`]'s caller should put each object in one output
+/// buffer (host only): (out_off, out_len, total bytes).
+pub fn ragged_layout(format: u8, sizes: &[u64], align: u64, stream_offset: u64) -> Result<(Vec<u64>, Vec<u64>, u64)> {
+    let (mut off, mut len, mut total) = (vec![0u64; sizes.len()], vec![0u64; sizes.len()], 0u64);
+    check(unsafe {
+        ffi_ext::chipx_ragged_layout(format, sizes.as_ptr(), sizes.len() as u64, align, stream_offset, off.as_mut_ptr(),
+                                     len.as_mut_ptr(), &mut total)
+    })?;
+    Ok((off, len, total))
+}
+
+pub fn ragged_scratch_len(format: u8, lens: &[u64], decode: bool) -> u64 {
+    unsafe { ffi_ext::chipx_ragged_scratch_len(format, lens.as_ptr(), lens.len() as u64, decode as c_int) }
+}
+
+/// encode() at a device-only level of objects of DIFFERENT lengths in one
+/// call (include/carbonado_hip_ext.h): object o = `input[in_off[o]..][..sizes[o]]`
+/// into `out[out_off[o]..]`, its hash to `hashes[32 o..]`.  Returns the encoded
+/// length and EncodeInfo of every object.  Enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn encode_ragged(format: u8, input: &DeviceBuffer, in_off: &[u64], sizes: &[u64], out: &mut DeviceBuffer,
+                     out_off: &[u64], hashes: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream)
+                     -> Result<(Vec<u64>, Vec<ChipEncodeInfo>)> {
+    let count = sizes.len();
+    if in_off.len() != count || out_off.len() != count || hashes.len() < count * HASH_LEN ||
+        (scratch.len() as u64) < ragged_scratch_len(format, sizes, false) ||
+        in_off.iter().zip(sizes).any(|(&o, &n)| o + n > input.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (_, need, _) = ragged_layout(format, sizes, 256, 0)?;
+    if out_off.iter().zip(&need).any(|(&o, &l)| o + l > out.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_ext()?;
+    let mut lens = vec![0u64; count];
+    let mut infos = vec![ChipEncodeInfo::default(); count];
+    check(unsafe {
+        ffi_ext::chipx_encode_ragged_dev(format, input.as_ptr(), in_off.as_ptr(), sizes.as_ptr(), count as u64,
+                                         out.as_mut_ptr(), out_off.as_ptr(), lens.as_mut_ptr(), hashes.as_mut_ptr(),
+                                         infos.as_mut_ptr(), scratch.ptr, stream.0)
+    })?;
+    Ok((lens, infos))
+}
+
+/// decode() of encodings of different lengths in one call; the per-object
+/// status (u32: 0 or 5 = hash mismatch) goes to `status` on the device.
+/// Returns the decoded lengths.  The bounds check is made before the lengths
+/// are known: `out` must hold `in_len[o]` bytes from `out_off[o]` (a decoding
+/// is never longer than its encoding).
+#[allow(clippy::too_many_arguments)]
+pub fn decode_ragged(format: u8, input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer,
+                     padding: &[u32], out: &mut DeviceBuffer, out_off: &[u64], status: &mut DeviceBuffer,
+                     scratch: &mut DeviceBuffer, stream: Stream) -> Result<Vec<u64>> {
+    let count = in_len.len();
+    if in_off.len() != count || out_off.len() != count || padding.len() != count ||
+        hashes.len() < count * HASH_LEN || status.len() < count * 4 ||
+        (scratch.len() as u64) < ragged_scratch_len(format, in_len, true) ||
+        in_off.iter().zip(in_len).any(|(&o, &l)| o + l > input.len() as u64) ||
+        // a decoding is never longer than its encoding
+        out_off.iter().zip(in_len).any(|(&o, &l)| o + l > out.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_ext()?;
+    let mut lens = vec![0u64; count];
+    check(unsafe {
+        ffi_ext::chipx_decode_ragged_dev(format, input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), count as u64,
+                                         hashes.as_ptr(), padding.as_ptr(), out.as_mut_ptr(), out_off.as_ptr(),
+                                         lens.as_mut_ptr(), status.as_mut_ptr() as *mut u32, scratch.ptr, stream.0)
+    })?;
+    Ok(lens)
 }
 
 /// scrub (decoding.rs:151-212) of every row: one result per stream

@@ -183,6 +183,21 @@ SIGNATURES = {
                                               ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32]),
 }
 
+# the extension header (include/carbonado_hip_ext.h): a table of its own, the
+# drop-in boundary above stays as it is
+EXT_SIGNATURES = {
+    "chipx_abi_version": (ctypes.c_int, []),
+    "chipx_ragged_layout": (ctypes.c_int, [ctypes.c_uint8, c_u64p, ctypes.c_uint64, ctypes.c_uint64,
+                                           ctypes.c_uint64, c_u64p, c_u64p, c_u64p]),
+    "chipx_ragged_scratch_len": (ctypes.c_uint64, [ctypes.c_uint8, c_u64p, ctypes.c_uint64, ctypes.c_int]),
+    "chipx_encode_ragged_dev": (ctypes.c_int, [ctypes.c_uint8, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_uint64,
+                                               ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p,
+                                               ctypes.POINTER(EncodeInfoC), ctypes.c_void_p, ctypes.c_void_p]),
+    "chipx_decode_ragged_dev": (ctypes.c_int, [ctypes.c_uint8, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_uint64,
+                                               ctypes.c_void_p, c_u32p, ctypes.c_void_p, c_u64p, c_u64p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -203,7 +218,7 @@ def lib() -> ctypes.CDLL:
         except ImportError:  # torch is plumbing only; the library does not need it
             pass
         l = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

@@ -251,6 +251,78 @@ def decode_host_batch(fmt: int, enc: torch.Tensor, in_len, hashes: torch.Tensor,
     return [olen[o] for o in range(count)], statuses
 
 
+# ---- ragged batches (include/carbonado_hip_ext.h): objects of different
+# lengths in one call; `inp` / `out` / `enc` are flat uint8 buffers and each
+# object has its own offset and length (host sequences of ints)
+
+def _u64(xs):
+    xs = [int(x) for x in xs]
+    return (ctypes.c_uint64 * max(len(xs), 1))(*xs), len(xs)
+
+
+def ragged_layout(fmt: int, sizes, align: int = 256, stream_offset: int = STREAM_OFFSET):
+    """Where encode_ragged's caller should put each object in one output
+    buffer (host only): rows rounded up to `align`, each encoding
+    `stream_offset` bytes into its row.  Returns (out_off, out_len, total)."""
+    n, count = _u64(sizes)
+    off, ln, total = (ctypes.c_uint64 * max(count, 1))(), (ctypes.c_uint64 * max(count, 1))(), ctypes.c_uint64()
+    check(_lib.lib().chipx_ragged_layout(fmt, n, count, align, stream_offset, off, ln, ctypes.byref(total)))
+    return list(off)[:count], list(ln)[:count], total.value
+
+
+def ragged_scratch(fmt: int, lens, decode: bool = False, device=None) -> torch.Tensor:
+    """Scratch of a ragged call over objects of these lengths (input lengths
+    of encode_ragged, encoded lengths of decode_ragged)."""
+    ln, count = _u64(lens)
+    size = _lib.lib().chipx_ragged_scratch_len(fmt, ln, count, int(decode))
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def encode_ragged(fmt: int, inp: torch.Tensor, in_off, sizes, out: torch.Tensor, out_off, hashes: torch.Tensor,
+                  scratch: torch.Tensor):
+    """encode() at Bao (4), Zfec (8) or both (12) of object o =
+    inp[in_off[o] : in_off[o] + sizes[o]] into out[out_off[o] :] (offsets as
+    ragged_layout gives them), its hash to hashes[o] (uint8 [count, 32]).
+    Returns (encoded length per object, EncodeInfo per object)."""
+    from .structs import EncodeInfo
+    assert inp.is_cuda and out.is_cuda and hashes.is_cuda and scratch.is_cuda
+    assert inp.dtype == out.dtype == torch.uint8 and inp.dim() == out.dim() == 1
+    assert inp.is_contiguous() and out.is_contiguous() and hashes.is_contiguous()
+    ioff, count = _u64(in_off)
+    n, _ = _u64(sizes)
+    ooff, _ = _u64(out_off)
+    assert len(sizes) == count == len(out_off) and hashes.numel() >= 32 * count
+    assert all(int(a) + int(b) <= inp.numel() for a, b in zip(in_off, sizes))
+    olen = (ctypes.c_uint64 * max(count, 1))()
+    info = (_lib.EncodeInfoC * max(count, 1))()
+    check(_lib.lib().chipx_encode_ragged_dev(fmt, _p(inp), ioff, n, count, _p(out), ooff, olen, _p(hashes), info,
+                                             _p(scratch), _stream()))
+    assert all(int(a) + b <= out.numel() for a, b in zip(out_off, list(olen)[:count]))
+    return list(olen)[:count], [EncodeInfo.from_c(info[o]) for o in range(count)]
+
+
+def decode_ragged(fmt: int, enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, out: torch.Tensor,
+                  out_off, status: torch.Tensor, scratch: torch.Tensor):
+    """decode() of the encodings enc[in_off[o] : in_off[o] + in_len[o]] with
+    hashes[o] and padding[o] into out[out_off[o] :]; status int32 / uint32
+    [count] on the device (0, or 5 = that object's hash mismatch).  Returns
+    the decoded length per object."""
+    assert enc.is_cuda and out.is_cuda and hashes.is_cuda and status.is_cuda and scratch.is_cuda
+    assert enc.dtype == out.dtype == torch.uint8 and enc.dim() == out.dim() == 1
+    assert enc.is_contiguous() and out.is_contiguous() and hashes.is_contiguous()
+    ioff, count = _u64(in_off)
+    ilen, _ = _u64(in_len)
+    ooff, _ = _u64(out_off)
+    pads = (ctypes.c_uint32 * max(count, 1))(*[int(x) for x in padding])
+    assert len(in_len) == count == len(out_off) == len(padding) and status.numel() >= count
+    assert all(int(a) + int(b) <= enc.numel() for a, b in zip(in_off, in_len))
+    olen = (ctypes.c_uint64 * max(count, 1))()
+    check(_lib.lib().chipx_decode_ragged_dev(fmt, _p(enc), ioff, ilen, count, _p(hashes), pads, _p(out), ooff, olen,
+                                             _p(status), _p(scratch), _stream()))
+    assert all(int(a) + b <= out.numel() for a, b in zip(out_off, list(olen)[:count]))
+    return list(olen)[:count]
+
+
 def host_topology() -> dict:
     """Where this process's host-copy path sits (chip_host_topology): the
     GPU's NUMA node, the calling thread's staging ring node and the copy
