@@ -9,7 +9,9 @@ routes where the maths allows:
   * BLAKE3 via the spec's incremental "CV stack" (merge while the chunk
     count has trailing zero bits), where the C oracle recurses on the
     left-subtree-size rule;
-  * bao layout by explicit pre-order recursion on node objects.
+  * bao layout by explicit pre-order recursion on node objects;
+  * bao slice verification (bao_decode_slice, authentic_shards), which the C
+    oracle does not have: the reference for scrub and verify_slice.
 References: zfec fec.c (fec_new, _invert_vdm, generate_gf); BLAKE3 paper
 section 2 and reference_impl.py; bao spec (combined encoding).
 """
@@ -263,11 +265,124 @@ def bao_slice(encoded: bytes, start: int, length: int) -> bytes:
             return
         left = 1 << ((c_cnt - 1).bit_length() - 1)
         hit = c_lo < last and c_lo + c_cnt > first
-        if hit:
-            out.append(encoded[pos:pos + 64])
+        if not hit:  # skip the subtree: its parents and its content bytes
+            pos += 64 * (c_cnt - 1) + min((c_lo + c_cnt) * 1024, n) - c_lo * 1024
+            return
+        out.append(encoded[pos:pos + 64])
         pos += 64
         walk(c_lo, left)
         walk(c_lo + left, c_cnt - left)
 
     walk(0, chunks)
     return b"".join(out)
+
+
+# ---------------- bao slice verification (SliceDecoder) ----------------
+class SliceError(Exception):
+    """bao_decode_slice: a node that does not hash to what its parent (or the
+    caller's hash) says, or a slice that ends early."""
+
+
+def _node_cv(kind: str, counter: int, data: bytes, root: bool, memo) -> bytes:
+    """CV (32 bytes) of a chunk or of a parent node's 64 stored bytes.  `memo`
+    {(kind, counter, bytes) -> CV} is a cache of this pure function: the real
+    hash fills it, bao_prime fills it from a stream already proven clean."""
+    key = (kind + "_root" if root else kind, counter, data)
+    if memo is not None and key in memo:
+        return memo[key]
+    if kind == "chunk":
+        o = _chunk_output(data, counter)
+    else:
+        w = struct.unpack("<16I", data)
+        o = _parent_output(list(w[:8]), list(w[8:]))
+    cv = struct.pack("<8I", *(o.root() if root else o.chaining_value()))
+    if memo is not None:
+        memo[key] = cv
+    return cv
+
+
+def bao_decode_slice(slice_bytes: bytes, hash: bytes, start: int, length: int, memo=None) -> bytes:
+    """bao's SliceDecoder over a combined-encoding slice (what decoding.rs:
+    132-149 runs): the pre-order walk of bao_slice's chunk range, every parent
+    node's 64 stored bytes and every chunk hashed and compared with the CV
+    its own parent stores (the root: with `hash`, under the ROOT flag; a
+    single-chunk stream is the root).  Raises SliceError at the first mismatch
+    or short read, else returns content [start, min(start + length, n))."""
+    if len(slice_bytes) < 8:
+        raise SliceError("short header")
+    n = struct.unpack("<Q", slice_bytes[:8])[0]
+    chunks = max(1, -(-n // 1024))
+    first = min(start // 1024, chunks - 1)
+    last = max(first + 1, min(-(-(start + length) // 1024), chunks))  # exclusive
+    pos = 8
+    got: list[bytes] = []
+
+    def take(size: int) -> bytes:
+        nonlocal pos
+        if pos + size > len(slice_bytes):
+            raise SliceError(f"short read at {pos}")
+        pos += size
+        return slice_bytes[pos - size:pos]
+
+    def walk(c_lo: int, c_cnt: int, want: bytes, root: bool) -> None:
+        if c_cnt == 1:
+            data = take(min(1024, n - c_lo * 1024))
+            if _node_cv("chunk", c_lo, data, root, memo) != want:
+                raise SliceError(f"chunk {c_lo}")
+            got.append(data)
+            return
+        node = take(64)
+        if _node_cv("parent", 0, node, root, memo) != want:
+            raise SliceError(f"parent of chunks [{c_lo}, {c_lo + c_cnt})")
+        left = 1 << ((c_cnt - 1).bit_length() - 1)
+        if c_lo + left > first:  # c_lo < last holds for every node reached
+            walk(c_lo, left, node[:32], False)
+        if c_lo + left < last:
+            walk(c_lo + left, c_cnt - left, node[32:], False)
+
+    walk(0, chunks, bytes(hash), True)
+    content = b"".join(got)
+    lo = start - first * 1024
+    return content[lo:lo + length] if start < n else b""
+
+
+def bao_prime(clean: bytes, hash: bytes, memo: dict | None = None) -> dict:
+    """The memo of a stream that the C oracle's bao_decode accepts under
+    `hash`: every node's CV is then the one its parent stores (the root's is
+    `hash`), so it is read from there instead of being hashed in Python.  A
+    node whose bytes differ from this stream misses the memo and is hashed."""
+    from . import oracle as O
+    O.bao_decode(clean, hash)  # raises unless the whole stream verifies
+    memo = {} if memo is None else memo
+    n = struct.unpack("<Q", clean[:8])[0]
+    pos = 8
+
+    def walk(c_lo, c_cnt, cv, root):
+        nonlocal pos
+        if c_cnt == 1:
+            size = min(1024, n - c_lo * 1024)
+            memo[("chunk_root" if root else "chunk", c_lo, clean[pos:pos + size])] = cv
+            pos += size
+            return
+        node = clean[pos:pos + 64]
+        pos += 64
+        memo[("parent_root" if root else "parent", 0, node)] = cv
+        left = 1 << ((c_cnt - 1).bit_length() - 1)
+        walk(c_lo, left, node[:32], False)
+        walk(c_lo + left, c_cnt - left, node[32:], False)
+
+    walk(0, max(1, -(-n // 1024)), bytes(hash), True)
+    return memo
+
+
+def authentic_shards(stream: bytes, hash: bytes, spc: int, memo=None) -> set[int]:
+    """The zfec shards (spc 1 KiB slices each) of a Bao|Zfec stream whose
+    slice verifies: what scrub (decoding.rs:172-183) may decode from."""
+    good = set()
+    for i in range(8):
+        try:
+            bao_decode_slice(bao_slice(stream, i * spc * 1024, spc * 1024), hash, i * spc * 1024, spc * 1024, memo)
+            good.add(i)
+        except SliceError:
+            pass
+    return good
