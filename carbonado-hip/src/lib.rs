@@ -22,6 +22,7 @@
 //! [`ChipError::NoDevice`].
 pub mod ffi;
 mod ffi_ext;
+mod ffi_audit;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -892,6 +893,130 @@ pub fn decode_ragged(format: u8, input: &DeviceBuffer, in_off: &[u64], in_len: &
         ffi_ext::chipx_decode_ragged_dev(format, input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), count as u64,
                                          hashes.as_ptr(), padding.as_ptr(), out.as_mut_ptr(), out_off.as_ptr(),
                                          lens.as_mut_ptr(), status.as_mut_ptr() as *mut u32, scratch.ptr, stream.0)
+    })?;
+    Ok(lens)
+}
+
+fn abi_audit() -> Result<()> {
+    abi()?;
+    match unsafe { ffi_audit::chipa_abi_version() } {
+        ffi_audit::CHIPA_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// The sizes and places of every slice request's proof and content (host
+/// only; include/carbonado_hip_audit.h).
+#[derive(Debug, Clone, Default)]
+pub struct SliceLayout {
+    pub proof_off: Vec<u64>,
+    pub proof_len: Vec<u64>,
+    pub content_off: Vec<u64>,
+    pub content_len: Vec<u64>,
+    pub proof_total: u64,
+    pub content_total: u64,
+}
+
+/// `content_len[r]` = the content length of request r's stream; request r is
+/// slices `[index[r], index[r] + count[r])` of 1024 bytes.
+pub fn slice_layout(content_len: &[u64], index: &[u64], count: &[u64], align: u64) -> Result<SliceLayout> {
+    let nreq = content_len.len();
+    if index.len() != nreq || count.len() != nreq {
+        return Err(ChipError::InvalidArgument);
+    }
+    let mut l = SliceLayout { proof_off: vec![0; nreq], proof_len: vec![0; nreq], content_off: vec![0; nreq],
+                              content_len: vec![0; nreq], proof_total: 0, content_total: 0 };
+    check(unsafe {
+        ffi_audit::chipa_slice_layout(content_len.as_ptr(), index.as_ptr(), count.as_ptr(), nreq as u64, align,
+                                      l.proof_off.as_mut_ptr(), l.proof_len.as_mut_ptr(), l.content_off.as_mut_ptr(),
+                                      l.content_len.as_mut_ptr(), &mut l.proof_total, &mut l.content_total)
+    })?;
+    Ok(l)
+}
+
+pub fn audit_scratch_len(nstreams: u64, nreq: u64) -> u64 {
+    unsafe { ffi_audit::chipa_audit_scratch_len(nstreams, nreq) }
+}
+
+/// extract_slice of every request from device-resident bao streams: request
+/// r's proof (stream `req_stream[r]` = `streams[in_off[s]..][..in_len[s]]`,
+/// slices `[index[r], index[r] + count[r])`) into `proofs[proof_off[r]..][..proof_len[r]]`,
+/// offsets and exact lengths as [`slice_layout`] gives them.  No hashing.
+/// Enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn extract_slices(streams: &DeviceBuffer, in_off: &[u64], in_len: &[u64], req_stream: &[u32], index: &[u64],
+                      count: &[u64], proofs: &mut DeviceBuffer, proof_off: &[u64], proof_len: &[u64],
+                      scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    let (nstreams, nreq) = (in_len.len(), req_stream.len());
+    if in_off.len() != nstreams || index.len() != nreq || count.len() != nreq || proof_off.len() != nreq ||
+        proof_len.len() != nreq || (scratch.len() as u64) < audit_scratch_len(nstreams as u64, nreq as u64) ||
+        in_off.iter().zip(in_len).any(|(&o, &l)| o + l > streams.len() as u64) ||
+        proof_off.iter().zip(proof_len).any(|(&o, &l)| o + l > proofs.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_audit()?;
+    check(unsafe {
+        ffi_audit::chipa_extract_slices_dev(streams.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), nstreams as u64,
+                                            req_stream.as_ptr(), index.as_ptr(), count.as_ptr(), nreq as u64,
+                                            proofs.as_mut_ptr(), proof_off.as_ptr(), proof_len.as_ptr(), scratch.ptr,
+                                            stream.0)
+    })
+}
+
+/// verify_slice of every request straight from the resident streams
+/// (`hashes[32 s..]` = stream s's hash): the per-request status (u32: 0 or 5 =
+/// hash mismatch) goes to `status` on the device, the content of request r to
+/// `content[content_off[r]..]` where its status is 0 and zeros otherwise.
+/// Returns the content lengths.  The bounds check is made before they are
+/// known: `content` must hold `count[r] * 1024` bytes from `content_off[r]`.
+#[allow(clippy::too_many_arguments)]
+pub fn verify_slices(streams: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer,
+                     req_stream: &[u32], index: &[u64], count: &[u64], content: &mut DeviceBuffer,
+                     content_off: &[u64], status: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream)
+                     -> Result<Vec<u64>> {
+    let (nstreams, nreq) = (in_len.len(), req_stream.len());
+    if in_off.len() != nstreams || index.len() != nreq || count.len() != nreq || content_off.len() != nreq ||
+        hashes.len() < nstreams * HASH_LEN || status.len() < nreq * 4 ||
+        (scratch.len() as u64) < audit_scratch_len(nstreams as u64, nreq as u64) ||
+        in_off.iter().zip(in_len).any(|(&o, &l)| o + l > streams.len() as u64) ||
+        content_off.iter().zip(count).any(|(&o, &c)| c > (1 << 53) || o + c * 1024 > content.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_audit()?;
+    let mut lens = vec![0u64; nreq];
+    check(unsafe {
+        ffi_audit::chipa_verify_slices_dev(streams.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), hashes.as_ptr(),
+                                           nstreams as u64, req_stream.as_ptr(), index.as_ptr(), count.as_ptr(),
+                                           nreq as u64, content.as_mut_ptr(), content_off.as_ptr(), lens.as_mut_ptr(),
+                                           status.as_mut_ptr() as *mut u32, scratch.ptr, stream.0)
+    })?;
+    Ok(lens)
+}
+
+/// The auditor's side of [`verify_slices`]: the same verdict and content from
+/// the proofs [`extract_slices`] wrote, without the streams.  `content_len[r]`
+/// = the content length of the stream request r's proof came from,
+/// `hashes[32 r..]` that stream's hash (one per request).
+#[allow(clippy::too_many_arguments)]
+pub fn verify_slice_proofs(proofs: &DeviceBuffer, proof_off: &[u64], proof_len: &[u64], content_len: &[u64],
+                           hashes: &DeviceBuffer, index: &[u64], count: &[u64], content: &mut DeviceBuffer,
+                           content_off: &[u64], status: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream)
+                           -> Result<Vec<u64>> {
+    let nreq = proof_len.len();
+    if proof_off.len() != nreq || content_len.len() != nreq || index.len() != nreq || count.len() != nreq ||
+        content_off.len() != nreq || hashes.len() < nreq * HASH_LEN || status.len() < nreq * 4 ||
+        (scratch.len() as u64) < audit_scratch_len(nreq as u64, nreq as u64) ||
+        proof_off.iter().zip(proof_len).any(|(&o, &l)| o + l > proofs.len() as u64) ||
+        content_off.iter().zip(count).any(|(&o, &c)| c > (1 << 53) || o + c * 1024 > content.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_audit()?;
+    let mut lens = vec![0u64; nreq];
+    check(unsafe {
+        ffi_audit::chipa_verify_proofs_dev(proofs.as_ptr(), proof_off.as_ptr(), proof_len.as_ptr(),
+                                           content_len.as_ptr(), hashes.as_ptr(), index.as_ptr(), count.as_ptr(),
+                                           nreq as u64, content.as_mut_ptr(), content_off.as_ptr(), lens.as_mut_ptr(),
+                                           status.as_mut_ptr() as *mut u32, scratch.ptr, stream.0)
     })?;
     Ok(lens)
 }

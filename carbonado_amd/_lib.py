@@ -198,6 +198,24 @@ EXT_SIGNATURES = {
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
+# the audit header (include/carbonado_hip_audit.h): slice audits of
+# device-resident streams, again a table of its own
+AUDIT_SIGNATURES = {
+    "chipa_abi_version": (ctypes.c_int, []),
+    "chipa_slice_layout": (ctypes.c_int, [c_u64p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_uint64, c_u64p, c_u64p,
+                                          c_u64p, c_u64p, c_u64p, c_u64p]),
+    "chipa_audit_scratch_len": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "chipa_extract_slices_dev": (ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_uint64, c_u32p, c_u64p,
+                                                c_u64p, ctypes.c_uint64, ctypes.c_void_p, c_u64p, c_u64p,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "chipa_verify_slices_dev": (ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p, ctypes.c_uint64,
+                                               c_u32p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p, c_u64p,
+                                               c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "chipa_verify_proofs_dev": (ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, c_u64p, ctypes.c_void_p, c_u64p,
+                                               c_u64p, ctypes.c_uint64, ctypes.c_void_p, c_u64p, c_u64p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -218,7 +236,7 @@ def lib() -> ctypes.CDLL:
         except ImportError:  # torch is plumbing only; the library does not need it
             pass
         l = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

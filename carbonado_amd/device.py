@@ -323,6 +323,149 @@ def decode_ragged(fmt: int, enc: torch.Tensor, in_off, in_len, hashes: torch.Ten
     return list(olen)[:count]
 
 
+# ---- slice audits (include/carbonado_hip_audit.h): extract_slice /
+# verify_slice for a batch of requests over device-resident bao streams.
+# `streams`, `proofs` and `content` are flat uint8 buffers; a request r is
+# (req_stream[r], index[r], count[r]) in units of 1024 bytes, as
+# decoding.verify_slice takes them
+
+def _arr(xs, dtype=np.uint64):
+    """(array, its pointer, its length) of a host sequence or numpy array; the
+    array stays referenced by the caller for the duration of the call."""
+    a = np.ascontiguousarray(xs, dtype=dtype).reshape(-1)
+    keep = a if a.size else np.zeros(1, dtype=dtype)
+    return keep, keep.ctypes.data_as(_lib.c_u64p if dtype == np.uint64 else _lib.c_u32p), int(a.size)
+
+
+def _fits(off, length, numel: int) -> bool:
+    """every range [off[r], off[r] + length[r]) lies inside a buffer of numel bytes"""
+    o, m = off[:length.size], np.uint64(numel)
+    return bool((o <= m).all() and (length <= m - np.minimum(o, m)).all())
+
+
+def _stream_content_lens(in_len):
+    """Content bytes of bao streams of in_len bytes: x = len - 8 = n + 64 (N - 1)
+    with N = ceil(n / 1024) chunks, so N - 1 = (x - 1) // 1088.  (A length no
+    stream has gives some number here: the call itself reports it.)"""
+    x = np.maximum(in_len, np.uint64(8)) - np.uint64(8)
+    return x - np.uint64(64) * ((np.maximum(x, np.uint64(1)) - np.uint64(1)) // np.uint64(1088))
+
+
+def _content_lens(ns, idx, cnt):
+    """min(n, start + len) - start where start < n, else 0, per request (the
+    content-buffer check made before a verify call; chipa_slice_layout's rule)"""
+    N = np.maximum((ns + np.uint64(1023)) // np.uint64(1024), np.uint64(1))
+    start = np.minimum(np.minimum(idx, N) * np.uint64(1024), ns)
+    end = np.minimum(np.minimum(idx + cnt, N) * np.uint64(1024), ns)
+    return np.where(end > start, end - start, np.uint64(0))
+
+
+def slice_layout(content_lens, index, count, align: int = 16):
+    """Sizes and places of every request's proof and content (host only):
+    content_lens[r] = the content length of request r's stream.  Returns
+    (proof_off, proof_len, content_off, content_len, proof_total,
+    content_total): offsets into one proof and one content buffer, each range
+    on a multiple of `align` (a multiple of 16)."""
+    n, pn, nreq = _arr(content_lens)
+    idx, pidx, ni = _arr(index)
+    cnt, pcnt, nc = _arr(count)
+    assert ni == nreq == nc
+    outs = [np.zeros(max(nreq, 1), dtype=np.uint64) for _ in range(4)]
+    pt, ct = ctypes.c_uint64(), ctypes.c_uint64()
+    check(_lib.lib().chipa_slice_layout(pn, pidx, pcnt, nreq, align, *[o.ctypes.data_as(_lib.c_u64p) for o in outs],
+                                        ctypes.byref(pt), ctypes.byref(ct)))
+    return (*[o[:nreq].tolist() for o in outs], pt.value, ct.value)
+
+
+def audit_scratch(nstreams: int, nreq: int, device=None) -> torch.Tensor:
+    """Scratch of an extract_slices / verify_slices / verify_slice_proofs call."""
+    size = _lib.lib().chipa_audit_scratch_len(nstreams, nreq)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def extract_slices(streams: torch.Tensor, in_off, in_len, req_stream, index, count, proofs: torch.Tensor,
+                   proof_off, proof_len, scratch: torch.Tensor) -> None:
+    """extract_slice of every request: the proof of request r (what
+    decoding.extract_slice(stream, index[r], count[r] * 1024) returns for stream
+    req_stream[r] = streams[in_off[s] : in_off[s] + in_len[s]]) into
+    proofs[proof_off[r] : proof_off[r] + proof_len[r]], the offsets and exact
+    lengths as slice_layout gives them.  No hashing, no status.  The per-stream
+    and per-request numbers are host sequences or numpy arrays."""
+    assert streams.is_cuda and proofs.is_cuda and scratch.is_cuda
+    assert streams.dtype == proofs.dtype == torch.uint8 and streams.dim() == proofs.dim() == 1
+    assert streams.is_contiguous() and proofs.is_contiguous()
+    ioff, pioff, nstreams = _arr(in_off)
+    ilen, pilen, nl = _arr(in_len)
+    rs, prs, nreq = _arr(req_stream, np.uint32)
+    idx, pidx, ni = _arr(index)
+    cnt, pcnt, nc = _arr(count)
+    poff, ppoff, npo = _arr(proof_off)
+    plen, pplen, npl = _arr(proof_len)
+    assert nl == nstreams and ni == nreq == nc == npo == npl
+    assert _fits(ioff, ilen[:nstreams], streams.numel()) and _fits(poff, plen[:nreq], proofs.numel())
+    assert scratch.numel() >= _lib.lib().chipa_audit_scratch_len(nstreams, nreq)
+    check(_lib.lib().chipa_extract_slices_dev(_p(streams), pioff, pilen, nstreams, prs, pidx, pcnt, nreq, _p(proofs),
+                                              ppoff, pplen, _p(scratch), _stream()))
+
+
+def verify_slices(streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, req_stream, index, count,
+                  content: torch.Tensor, content_off, status: torch.Tensor, scratch: torch.Tensor):
+    """verify_slice of every request straight from the resident streams;
+    hashes uint8 [nstreams, 32].  status int32 / uint32 [nreq] on the device:
+    0, or 5 where a node on the request's walk (or the stream's header, or its
+    hash) disagrees.  content[content_off[r] :] receives the request's content
+    where the status is 0 and zeros otherwise (offsets as slice_layout gives
+    them).  Returns the content length per request."""
+    assert streams.is_cuda and content.is_cuda and hashes.is_cuda and status.is_cuda and scratch.is_cuda
+    assert streams.dtype == content.dtype == torch.uint8 and streams.dim() == content.dim() == 1
+    assert streams.is_contiguous() and content.is_contiguous() and hashes.is_contiguous()
+    ioff, pioff, nstreams = _arr(in_off)
+    ilen, pilen, nl = _arr(in_len)
+    rs, prs, nreq = _arr(req_stream, np.uint32)
+    idx, pidx, ni = _arr(index)
+    cnt, pcnt, nc = _arr(count)
+    coff, pcoff, nco = _arr(content_off)
+    assert nl == nstreams and ni == nreq == nc == nco
+    assert hashes.numel() >= 32 * nstreams and status.numel() >= nreq and status.element_size() == 4
+    assert _fits(ioff, ilen[:nstreams], streams.numel())
+    assert scratch.numel() >= _lib.lib().chipa_audit_scratch_len(nstreams, nreq)
+    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
+    if nreq and int(rs.max()) < nstreams:  # the content buffer is checked before the call (else: the call reports it)
+        assert _fits(coff, _content_lens(_stream_content_lens(ilen)[rs[:nreq]], idx[:nreq], cnt[:nreq]), content.numel())
+    check(_lib.lib().chipa_verify_slices_dev(_p(streams), pioff, pilen, _p(hashes), nstreams, prs, pidx, pcnt, nreq,
+                                             _p(content), pcoff, clen.ctypes.data_as(_lib.c_u64p), _p(status),
+                                             _p(scratch), _stream()))
+    return clen[:nreq].tolist()
+
+
+def verify_slice_proofs(proofs: torch.Tensor, proof_off, proof_len, content_lens, hashes: torch.Tensor, index, count,
+                        content: torch.Tensor, content_off, status: torch.Tensor, scratch: torch.Tensor):
+    """The auditor's side: verify_slice from extracted proofs alone.  Request
+    r's proof is proofs[proof_off[r] : proof_off[r] + proof_len[r]],
+    content_lens[r] the content length of the stream it came from, hashes
+    uint8 [nreq, 32] that stream's hash (one per request).  status and content
+    as verify_slices.  Returns the content length per request."""
+    assert proofs.is_cuda and content.is_cuda and hashes.is_cuda and status.is_cuda and scratch.is_cuda
+    assert proofs.dtype == content.dtype == torch.uint8 and proofs.dim() == content.dim() == 1
+    assert proofs.is_contiguous() and content.is_contiguous() and hashes.is_contiguous()
+    poff, ppoff, nreq = _arr(proof_off)
+    plen, pplen, npl = _arr(proof_len)
+    n, pn, nn = _arr(content_lens)
+    idx, pidx, ni = _arr(index)
+    cnt, pcnt, nc = _arr(count)
+    coff, pcoff, nco = _arr(content_off)
+    assert npl == nreq == nn == ni == nc == nco
+    assert hashes.numel() >= 32 * nreq and status.numel() >= nreq and status.element_size() == 4
+    assert _fits(poff, plen[:nreq], proofs.numel())
+    assert scratch.numel() >= _lib.lib().chipa_audit_scratch_len(nreq, nreq)
+    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
+    assert _fits(coff, _content_lens(n[:nreq], idx[:nreq], cnt[:nreq]), content.numel())  # before the call
+    check(_lib.lib().chipa_verify_proofs_dev(_p(proofs), ppoff, pplen, pn, _p(hashes), pidx, pcnt, nreq, _p(content),
+                                             pcoff, clen.ctypes.data_as(_lib.c_u64p), _p(status), _p(scratch),
+                                             _stream()))
+    return clen[:nreq].tolist()
+
+
 def host_topology() -> dict:
     """Where this process's host-copy path sits (chip_host_topology): the
     GPU's NUMA node, the calling thread's staging ring node and the copy
