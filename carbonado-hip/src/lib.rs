@@ -23,6 +23,7 @@
 pub mod ffi;
 mod ffi_ext;
 mod ffi_audit;
+mod ffi_repair;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -1037,6 +1038,71 @@ pub fn scrub_batch(input: &DeviceRows, len: u64, hashes: &DeviceBuffer, padding:
     check(unsafe {
         ffi::chip_scrub_batch_dev(input.as_ptr(), input.stride, len, input.count, hashes.as_ptr(), padding, chunk_len,
                                   out.as_mut_ptr(), out.stride, status.as_mut_ptr(), scratch.ptr, stream.0)
+    })?;
+    Ok(status.into_iter().map(check).collect())
+}
+
+fn abi_repair() -> Result<()> {
+    abi()?;
+    match unsafe { ffi_repair::chipr_abi_version() } {
+        ffi_repair::CHIPR_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// Scratch of a [`scrub_ragged`] / [`shard_masks_ragged`] call over streams of
+/// these lengths that repairs any `nrepair` of them per pass (`in_len.len()`:
+/// one pass; 1: the least a call accepts).
+pub fn scrub_ragged_scratch_len(in_len: &[u64], nrepair: u64) -> u64 {
+    unsafe { ffi_repair::chipr_scrub_ragged_scratch_len(in_len.as_ptr(), in_len.len() as u64, nrepair) }
+}
+
+/// The authentic zfec shards of every resident Bao|Zfec stream (stream o =
+/// `input[in_off[o]..][..in_len[o]]`, `hashes[32 o..]` its hash, `chunk_len[o]`
+/// its EncodeInfo's): `masks` (u32 per stream, on the device) gets bit i set
+/// when shard i verifies; 0xFF = intact.  Enqueued on `stream`, not
+/// synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn shard_masks_ragged(input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer,
+                          chunk_len: &[u32], masks: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream)
+                          -> Result<()> {
+    let count = in_len.len();
+    if in_off.len() != count || chunk_len.len() != count || hashes.len() < count * HASH_LEN ||
+        masks.len() < count * 4 || in_off.iter().zip(in_len).any(|(&o, &l)| o + l > input.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_repair()?;
+    check(unsafe {
+        ffi_repair::chipr_shard_masks_ragged_dev(input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), count as u64,
+                                                 hashes.as_ptr(), chunk_len.as_ptr(), masks.as_mut_ptr() as *mut u32,
+                                                 scratch.ptr, scratch.len() as u64, stream.0)
+    })
+}
+
+/// scrub (decoding.rs:151-212) of resident Bao|Zfec streams of different
+/// lengths in one call: one result per stream (Ok = repaired into
+/// `out[out_off[o]..][..in_len[o]]`; UnnecessaryScrub = intact; an output
+/// range is written only for Ok).  The repairs run in as many passes as
+/// `scratch` requires ([`scrub_ragged_scratch_len`]).  Synchronous.  (In place
+/// repair, where output and input ranges coincide, needs the raw call: here
+/// `out` is borrowed apart from `input`.)
+#[allow(clippy::too_many_arguments)]
+pub fn scrub_ragged(input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer, padding: &[u32],
+                    chunk_len: &[u32], out: &mut DeviceBuffer, out_off: &[u64], scratch: &mut DeviceBuffer,
+                    stream: Stream) -> Result<Vec<Result<()>>> {
+    let count = in_len.len();
+    if in_off.len() != count || padding.len() != count || chunk_len.len() != count || out_off.len() != count ||
+        hashes.len() < count * HASH_LEN || in_off.iter().zip(in_len).any(|(&o, &l)| o + l > input.len() as u64) ||
+        out_off.iter().zip(in_len).any(|(&o, &l)| o + l > out.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_repair()?;
+    let mut status = vec![0i32; count];
+    check(unsafe {
+        ffi_repair::chipr_scrub_ragged_dev(input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), count as u64,
+                                           hashes.as_ptr(), padding.as_ptr(), chunk_len.as_ptr(), out.as_mut_ptr(),
+                                           out_off.as_ptr(), status.as_mut_ptr(), scratch.ptr, scratch.len() as u64,
+                                           stream.0)
     })?;
     Ok(status.into_iter().map(check).collect())
 }

@@ -216,6 +216,19 @@ AUDIT_SIGNATURES = {
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
+# the repair header (include/carbonado_hip_repair.h): the ragged scrub of
+# device-resident Bao|Zfec streams, a fourth table of its own
+REPAIR_SIGNATURES = {
+    "chipr_abi_version": (ctypes.c_int, []),
+    "chipr_scrub_ragged_scratch_len": (ctypes.c_uint64, [c_u64p, ctypes.c_uint64, ctypes.c_uint64]),
+    "chipr_shard_masks_ragged_dev": (ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                                    c_u32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                    ctypes.c_void_p]),
+    "chipr_scrub_ragged_dev": (ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p, c_u32p,
+                                              c_u32p, ctypes.c_void_p, c_u64p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_uint64, ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -236,7 +249,7 @@ def lib() -> ctypes.CDLL:
         except ImportError:  # torch is plumbing only; the library does not need it
             pass
         l = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

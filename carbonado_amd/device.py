@@ -466,6 +466,74 @@ def verify_slice_proofs(proofs: torch.Tensor, proof_off, proof_len, content_lens
     return clen[:nreq].tolist()
 
 
+# ---- ragged scrub (include/carbonado_hip_repair.h): shard verdicts and repair
+# of device-resident Bao|Zfec streams of different lengths in one call.  `enc`
+# and `out` are flat uint8 buffers; stream o is enc[in_off[o] : in_off[o] +
+# in_len[o]] with its own padding[o] and chunk_len[o] (EncodeInfo's)
+
+def scrub_ragged_scratch(in_len, nrepair=None, device=None) -> torch.Tensor:
+    """Scratch of a scrub_ragged / shard_masks_ragged call over streams of
+    these lengths that repairs any `nrepair` of them per pass (None: all of
+    them, one pass; 1: the least a call accepts)."""
+    ln, pl, count = _arr(in_len)
+    size = _lib.lib().chipr_scrub_ragged_scratch_len(pl, count, count if nrepair is None else int(nrepair))
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def shard_masks_ragged(enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, chunk_len,
+                       scratch: torch.Tensor, masks: torch.Tensor | None = None) -> torch.Tensor:
+    """The authentic zfec shards of every stream (decoding.rs:172-183): returns
+    masks int32 [count] on the device, bit i set when shard i of stream o
+    verifies against hashes[o] (uint8 [count, 32]); 255 = intact, 0 also for a
+    damaged header or a chunk_len that does not fit the stream.  Enqueued on
+    the current stream, not synchronised."""
+    assert enc.is_cuda and hashes.is_cuda and scratch.is_cuda
+    assert enc.dtype == torch.uint8 and enc.dim() == 1 and enc.is_contiguous() and hashes.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ilen, pilen, nl = _arr(in_len)
+    cl, pcl, ncl = _arr(chunk_len, np.uint32)
+    assert nl == count == ncl and hashes.numel() >= 32 * count
+    assert _fits(ioff, ilen[:count], enc.numel())
+    if masks is None:
+        masks = torch.empty(count, dtype=torch.int32, device=enc.device)
+    assert masks.is_cuda and masks.numel() >= count and masks.element_size() == 4 and masks.is_contiguous()
+    check(_lib.lib().chipr_shard_masks_ragged_dev(_p(enc), pioff, pilen, count, _p(hashes), pcl, _p(masks), _p(scratch),
+                                                  scratch.numel(), _stream()))
+    return masks
+
+
+def scrub_ragged(enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len, out: torch.Tensor,
+                 out_off, scratch: torch.Tensor) -> np.ndarray:
+    """scrub() (decoding.rs:151-212) of device-resident Bao|Zfec streams of
+    different lengths in one call: stream o = enc[in_off[o] : in_off[o] +
+    in_len[o]] with hashes[o] (uint8 [count, 32]), padding[o] and chunk_len[o];
+    a repaired stream goes to out[out_off[o] : out_off[o] + in_len[o]].
+    Returns the per-object statuses (int32 numpy), what scrub_batch gives for
+    that stream alone: 0 = repaired, CHIP_ERR_UNNECESSARY_SCRUB = intact, else
+    scrub's error (a chunk_len that does not fit its stream is that object's
+    ZfecError, not the call's).  An output range is written only where the
+    status is 0 (its repaired stream's hash matched), and then completely;
+    nothing else of `out` is touched.  `out` may be `enc` with out_off[o] ==
+    in_off[o]: the stream is repaired where it lies.  The repairs run in as
+    many passes as `scratch` requires (scrub_ragged_scratch); the results do
+    not depend on it.  Synchronous."""
+    assert enc.is_cuda and out.is_cuda and hashes.is_cuda and scratch.is_cuda
+    assert enc.dtype == out.dtype == torch.uint8 and enc.dim() == out.dim() == 1
+    assert enc.is_contiguous() and out.is_contiguous() and hashes.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ilen, pilen, nl = _arr(in_len)
+    ooff, pooff, no = _arr(out_off)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    cl, pcl, ncl = _arr(chunk_len, np.uint32)
+    assert nl == count == no == npad == ncl and hashes.numel() >= 32 * count
+    assert _fits(ioff, ilen[:count], enc.numel()) and _fits(ooff, ilen[:count], out.numel())
+    status = np.zeros(max(count, 1), dtype=np.int32)
+    check(_lib.lib().chipr_scrub_ragged_dev(_p(enc), pioff, pilen, count, _p(hashes), ppad, pcl, _p(out), pooff,
+                                            status.ctypes.data_as(ctypes.c_void_p), _p(scratch), scratch.numel(),
+                                            _stream()))
+    return status[:count]
+
+
 def host_topology() -> dict:
     """Where this process's host-copy path sits (chip_host_topology): the
     GPU's NUMA node, the calling thread's staging ring node and the copy
