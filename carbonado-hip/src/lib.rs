@@ -24,6 +24,7 @@ pub mod ffi;
 mod ffi_ext;
 mod ffi_audit;
 mod ffi_repair;
+mod ffi_read;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -1105,6 +1106,72 @@ pub fn scrub_ragged(input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes
                                            stream.0)
     })?;
     Ok(status.into_iter().map(check).collect())
+}
+
+fn abi_read() -> Result<()> {
+    abi()?;
+    match unsafe { ffi_read::chipd_abi_version() } {
+        ffi_read::CHIPD_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// Where a [`read_ranges`] caller puts every request's content (host only):
+/// (content_off, content_len, content_total, nseg), every range on a multiple
+/// of `align` (a multiple of 16); `nseg` is for [`read_scratch_len`].
+pub fn read_layout(chunk_len: &[u32], padding: &[u32], req_stream: &[u32], start: &[u64], len: &[u64], align: u64)
+                   -> Result<(Vec<u64>, Vec<u64>, u64, u64)> {
+    let nreq = req_stream.len();
+    if padding.len() != chunk_len.len() || start.len() != nreq || len.len() != nreq {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (mut off, mut clen, mut total, mut nseg) = (vec![0u64; nreq], vec![0u64; nreq], 0u64, 0u64);
+    check(unsafe {
+        ffi_read::chipd_read_layout(chunk_len.as_ptr(), padding.as_ptr(), chunk_len.len() as u64, req_stream.as_ptr(),
+                                    start.as_ptr(), len.as_ptr(), nreq as u64, align, off.as_mut_ptr(),
+                                    clen.as_mut_ptr(), &mut total, &mut nseg)
+    })?;
+    Ok((off, clen, total, nseg))
+}
+
+/// Scratch of a [`read_ranges`] call of `nreq` requests in `nseg` segments.
+pub fn read_scratch_len(nreq: u64, nseg: u64) -> u64 {
+    unsafe { ffi_read::chipd_read_scratch_len(nreq, nseg) }
+}
+
+/// Object bytes `[start[r], start[r] + len[r])` of resident Zfec|Bao stream
+/// `req_stream[r]` (stream s = `input[in_off[s]..][..in_len[s]]`) into
+/// `content[content_off[r]..]`: copied where the primary's chunks verify,
+/// rebuilt from four other authentic shards where they do not.  `status` and
+/// `used` (u32 per request, on the device) get 0 or 7 and the shards each
+/// request was served from.  Enqueued on `stream`, not synchronised.  Returns
+/// the content length per request.
+#[allow(clippy::too_many_arguments)]
+pub fn read_ranges(input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer, padding: &[u32],
+                   chunk_len: &[u32], req_stream: &[u32], start: &[u64], len: &[u64], content: &mut DeviceBuffer,
+                   content_off: &[u64], status: &mut DeviceBuffer, used: &mut DeviceBuffer, scratch: &mut DeviceBuffer,
+                   stream: Stream) -> Result<Vec<u64>> {
+    let (count, nreq) = (in_len.len(), req_stream.len());
+    if in_off.len() != count || padding.len() != count || chunk_len.len() != count || start.len() != nreq ||
+        len.len() != nreq || content_off.len() != nreq || hashes.len() < count * HASH_LEN ||
+        status.len() < nreq * 4 || used.len() < nreq * 4 ||
+        in_off.iter().zip(in_len).any(|(&o, &l)| o + l > input.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (_, want, _, _) = read_layout(chunk_len, padding, req_stream, start, len, 16)?;
+    if content_off.iter().zip(&want).any(|(&o, &l)| o + l > content.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_read()?;
+    let mut clen = vec![0u64; nreq];
+    check(unsafe {
+        ffi_read::chipd_read_ranges_dev(input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), hashes.as_ptr(),
+                                        padding.as_ptr(), chunk_len.as_ptr(), count as u64, req_stream.as_ptr(),
+                                        start.as_ptr(), len.as_ptr(), nreq as u64, content.as_mut_ptr(),
+                                        content_off.as_ptr(), clen.as_mut_ptr(), status.as_mut_ptr() as *mut u32,
+                                        used.as_mut_ptr() as *mut u32, scratch.ptr, scratch.len() as u64, stream.0)
+    })?;
+    Ok(clen)
 }
 
 /// encode() of `count` objects in HOST memory, H2D / kernels / D2H and the

@@ -229,6 +229,19 @@ REPAIR_SIGNATURES = {
                                               ctypes.c_uint64, ctypes.c_void_p]),
 }
 
+# the read header (include/carbonado_hip_read.h): ranged reads of resident
+# Zfec|Bao objects that survive shard damage, a fifth table of its own
+READ_SIGNATURES = {
+    "chipd_abi_version": (ctypes.c_int, []),
+    "chipd_read_layout": (ctypes.c_int, [c_u32p, c_u32p, ctypes.c_uint64, c_u32p, c_u64p, c_u64p, ctypes.c_uint64,
+                                         ctypes.c_uint64, c_u64p, c_u64p, c_u64p, c_u64p]),
+    "chipd_read_scratch_len": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "chipd_read_ranges_dev": (ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p, c_u32p, c_u32p,
+                                             ctypes.c_uint64, c_u32p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                             c_u64p, c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_uint64, ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -249,7 +262,8 @@ def lib() -> ctypes.CDLL:
         except ImportError:  # torch is plumbing only; the library does not need it
             pass
         l = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES,
+                                  **READ_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

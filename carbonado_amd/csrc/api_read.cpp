@@ -1,0 +1,76 @@
+// api_read.cpp — the ranged reads of include/carbonado_hip_read.h: byte ranges
+// of device-resident Zfec|Bao objects, rebuilt from other shards where the
+// primary's chunks are damaged.  The checks, the layout, the segments and
+// every table are host code in read_plan.hpp; this file uploads the table into
+// the caller's scratch and enqueues KA's checks of the primary slices
+// (audit_kernels.hip) and the kernels of read_kernels.hip behind it.
+#include "api_common.hpp"
+#include "audit_kernels.hpp"
+#include "read_kernels.hpp"
+
+using namespace chip;
+using namespace chip::api;
+
+extern "C" {
+
+int chipd_abi_version(void) { return CHIPD_ABI_VERSION; }
+
+int chipd_read_layout(const uint32_t *chunk_len, const uint32_t *padding, uint64_t nstreams, const uint32_t *req_stream,
+                      const uint64_t *start, const uint64_t *len, uint64_t nreq, uint64_t align, uint64_t *content_off,
+                      uint64_t *content_len, uint64_t *content_total, uint64_t *nseg) {
+    return read::layout(chunk_len, padding, nstreams, req_stream, start, len, nreq, align, content_off, content_len,
+                        content_total, nseg);
+}
+
+uint64_t chipd_read_scratch_len(uint64_t nreq, uint64_t nseg) { return read::scratch_len(nreq, nseg); }
+
+int chipd_read_ranges_dev(const uint8_t *d_streams, const uint64_t *in_off, const uint64_t *in_len,
+                          const uint8_t *d_hash, const uint32_t *padding, const uint32_t *chunk_len, uint64_t nstreams,
+                          const uint32_t *req_stream, const uint64_t *start, const uint64_t *len, uint64_t nreq,
+                          uint8_t *d_content, const uint64_t *content_off, uint64_t *content_len, uint32_t *d_status,
+                          uint32_t *d_used, void *d_scratch, uint64_t scratch_len, void *stream) {
+    if (nreq == 0) return CHIP_OK;
+    read::Plan p;
+    int st = read::plan_read(reinterpret_cast<uintptr_t>(d_streams), in_off, in_len, reinterpret_cast<uintptr_t>(d_hash),
+                             padding, chunk_len, nstreams, req_stream, start, len, nreq,
+                             reinterpret_cast<uintptr_t>(d_content), content_off, content_len, d_status && d_used,
+                             reinterpret_cast<uintptr_t>(d_scratch), scratch_len, &p);
+    if (st != CHIP_OK) return st;
+    st = use_device();
+    if (st != CHIP_OK) return st;
+    Ctx *c;
+    st = ctx_get(&c);
+    if (st != CHIP_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t *scr = static_cast<uint8_t *>(d_scratch);
+    const audit::ScratchLayout &ka = p.ka.lay;
+    CHIP_HIP(h2d(c->stage, scr, p.ka.table.data(), p.ka.table.size(), s));
+    ReadLaunch L{};
+    L.slices = reinterpret_cast<const audit::Req *>(scr + p.lay.audit + ka.reqs);
+    L.parents = reinterpret_cast<const uint64_t *>(scr + p.lay.audit + ka.parents);
+    L.chunks = reinterpret_cast<const uint64_t *>(scr + p.lay.audit + ka.chunks);
+    L.masks = reinterpret_cast<const read::MaskEntry *>(scr + p.lay.masks);
+    L.reqs = reinterpret_cast<const read::Req *>(scr + p.lay.reqs);
+    L.segs = reinterpret_cast<const read::Seg *>(scr + p.lay.segs);
+    L.fpar = reinterpret_cast<const uint64_t *>(scr + p.lay.fpar);
+    L.blocks = reinterpret_cast<const uint64_t *>(scr + p.lay.blocks);
+    L.rstat = reinterpret_cast<uint32_t *>(scr + p.lay.rstat);
+    L.served = reinterpret_cast<read::Served *>(scr + p.lay.served);
+    L.nreq = p.nreq; L.nseg = p.nseg; L.total_blocks = p.total_blocks;
+    L.prim_parents = p.prim_parents; L.prim_chunks = p.prim_chunks; L.fb_parents = p.fb_parents;
+    L.status = d_status; L.used = d_used;
+    if (p.nseg) {
+        CHIP_HIP(hipMemsetAsync(L.rstat, 0, read::M * p.nseg * sizeof(uint32_t), s));
+        AuditLaunch A{};  // KA's checks of every segment's own slice
+        A.reqs = L.slices; A.parents = L.parents; A.chunks = L.chunks; A.units = nullptr;
+        A.nreq = p.nseg; A.total_parents = p.prim_parents; A.total_chunks = p.prim_chunks; A.total_units = 0;
+        A.proofs = false;
+        A.status = L.rstat;
+        CHIP_HIP(audit_verify_launch(A, s));
+        CHIP_HIP(read_fallback_launch(L, s));
+    }
+    CHIP_HIP(read_serve_launch(L, s));
+    return CHIP_OK;
+}
+
+}  // extern "C"

@@ -60,11 +60,6 @@ __device__ __forceinline__ uint32_t find_rep64(const uint64_t *pre, uint32_t nre
     return lo;
 }
 
-// four bytes of GF(2^8) mod 0x11D doubled at once
-__device__ __forceinline__ uint32_t gf_double4(uint32_t c) {
-    return ((c & 0x7F7F7F7Fu) << 1) ^ (((c >> 7) & 0x01010101u) * 0x1Du);
-}
-
 // 16 B of the four output rows from 16 B at the same position of each input
 // (ragged_kernels.hip parity16: the packed table in LDS, a 4 x 4 transpose)
 __device__ __forceinline__ void product16(const uint32_t *tab, const u32x4 (&v)[4], u32x4 (&p)[4]) {
@@ -100,7 +95,7 @@ __global__ __launch_bounds__(TPB) void repair_decode_kernel(const Rec *recs, con
 #pragma unroll
         for (int bit = 0; bit < 8; ++bit) {
             if (x >> bit & 1) acc ^= cw;
-            cw = gf_double4(cw);
+            cw = zf::gf_double4(cw);
         }
         tab[s * 256 + x] = acc;
     }

@@ -177,6 +177,11 @@ __device__ __forceinline__ uint32_t comp(const u32x4 &v, int d) {
     return d == 0 ? v.x : d == 1 ? v.y : d == 2 ? v.z : v.w;
 }
 
+// four bytes of GF(2^8) mod 0x11D doubled at once
+__device__ __forceinline__ uint32_t gf_double4(uint32_t c) {
+    return ((c & 0x7F7F7F7Fu) << 1) ^ (((c >> 7) & 0x01010101u) * 0x1Du);
+}
+
 // Tile schedule (MAP), per workgroup b of G:
 //   0  grid-stride: tile = b, b + G, b + 2G, ...
 //   1  XCD-grouped grid-stride: the G/8 workgroups that share an XCD

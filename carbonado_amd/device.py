@@ -534,6 +534,72 @@ def scrub_ragged(enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, paddin
     return status[:count]
 
 
+# ---- ranged reads (include/carbonado_hip_read.h): byte ranges of resident
+# Zfec|Bao objects, rebuilt from other shards where the primary's chunks are
+# damaged.  A request r is (req_stream[r], start[r], len[r]) in object bytes
+
+def read_layout(chunk_len, padding, req_stream, start, length, align: int = 16):
+    """Where read_ranges' caller should put every request's content (host
+    only).  Returns (content_off, content_len, content_total, nseg): offsets
+    into one content buffer, each range on a multiple of `align` (a multiple of
+    16), and the segments of the call for read_scratch."""
+    cl, pcl, nstreams = _arr(chunk_len, np.uint32)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    rs, prs, nreq = _arr(req_stream, np.uint32)
+    st, pst, ns = _arr(start)
+    ln, pln, nl = _arr(length)
+    assert npad == nstreams and ns == nreq == nl
+    off, clen = np.zeros(max(nreq, 1), dtype=np.uint64), np.zeros(max(nreq, 1), dtype=np.uint64)
+    total, nseg = ctypes.c_uint64(), ctypes.c_uint64()
+    check(_lib.lib().chipd_read_layout(pcl, ppad, nstreams, prs, pst, pln, nreq, align, off.ctypes.data_as(_lib.c_u64p),
+                                       clen.ctypes.data_as(_lib.c_u64p), ctypes.byref(total), ctypes.byref(nseg)))
+    return off[:nreq].tolist(), clen[:nreq].tolist(), total.value, nseg.value
+
+
+def read_scratch(nreq: int, nseg: int, device=None) -> torch.Tensor:
+    """Scratch of a read_ranges call of nreq requests in nseg segments (read_layout)."""
+    size = _lib.lib().chipd_read_scratch_len(nreq, nseg)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def read_ranges(streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len, req_stream, start,
+                length, content: torch.Tensor, content_off, status: torch.Tensor, used: torch.Tensor,
+                scratch: torch.Tensor):
+    """Object bytes [start[r], start[r] + length[r]) of stream req_stream[r] =
+    streams[in_off[s] : in_off[s] + in_len[s]] (hashes uint8 [nstreams, 32],
+    padding[s] and chunk_len[s] its EncodeInfo's) into content[content_off[r] :]
+    (offsets as read_layout gives them).  A range whose primary chunks verify
+    is copied; one whose chunks are damaged is rebuilt from the first four
+    shards whose chunks at the same place verify.  status int32 / uint32 [nreq]
+    on the device: 0, or 7 where fewer than four do (zeros are written);
+    used [nreq]: the shards each request was served from (bit p alone: copied
+    from primary p).  Enqueued on the current stream, not synchronised.
+    Returns the content length per request."""
+    assert streams.is_cuda and content.is_cuda and hashes.is_cuda and status.is_cuda and used.is_cuda and scratch.is_cuda
+    assert streams.dtype == content.dtype == torch.uint8 and streams.dim() == content.dim() == 1
+    assert streams.is_contiguous() and content.is_contiguous() and hashes.is_contiguous()
+    ioff, pioff, nstreams = _arr(in_off)
+    ilen, pilen, nl = _arr(in_len)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    cl, pcl, ncl = _arr(chunk_len, np.uint32)
+    rs, prs, nreq = _arr(req_stream, np.uint32)
+    st, pst, ns = _arr(start)
+    ln, pln, nln = _arr(length)
+    coff, pcoff, nco = _arr(content_off)
+    assert nl == nstreams == npad == ncl and ns == nreq == nln == nco
+    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
+    for t in (status, used):
+        assert t.numel() >= nreq and t.element_size() == 4 and t.is_contiguous()
+    if nreq and int(rs.max()) < nstreams:  # the content buffer is checked before the call (else: the call reports it)
+        _, want, _, _ = read_layout(cl[:nstreams], pad[:nstreams], rs[:nreq], st[:nreq], ln[:nreq])
+        assert _fits(coff, np.asarray(want, dtype=np.uint64), content.numel())
+    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
+    check(_lib.lib().chipd_read_ranges_dev(_p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams, prs, pst, pln,
+                                           nreq, _p(content), pcoff, clen.ctypes.data_as(_lib.c_u64p), _p(status),
+                                           _p(used), _p(scratch), scratch.numel(), _stream()))
+    return clen[:nreq].tolist()
+
+
 def host_topology() -> dict:
     """Where this process's host-copy path sits (chip_host_topology): the
     GPU's NUMA node, the calling thread's staging ring node and the copy
