@@ -25,6 +25,7 @@ mod ffi_ext;
 mod ffi_audit;
 mod ffi_repair;
 mod ffi_read;
+mod ffi_vread;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -1170,6 +1171,66 @@ pub fn read_ranges(input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes:
                                         start.as_ptr(), len.as_ptr(), nreq as u64, content.as_mut_ptr(),
                                         content_off.as_ptr(), clen.as_mut_ptr(), status.as_mut_ptr() as *mut u32,
                                         used.as_mut_ptr() as *mut u32, scratch.ptr, scratch.len() as u64, stream.0)
+    })?;
+    Ok(clen)
+}
+
+fn abi_vread() -> Result<()> {
+    abi_read()?;
+    match unsafe { ffi_vread::chipv_abi_version() } {
+        ffi_vread::CHIPV_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// Bits of a request's vouch word ([`read_ranges_vouched`]).
+pub const VOUCHED: u32 = ffi_vread::CHIPV_VOUCHED;
+pub const UNVOUCHED: u32 = ffi_vread::CHIPV_UNVOUCHED;
+pub const CONTRADICTED: u32 = ffi_vread::CHIPV_CONTRADICTED;
+/// Flag of [`read_ranges_vouched`]: a request with an unvouched segment fails with 7.
+pub const VREAD_STRICT: u32 = ffi_vread::CHIPV_STRICT;
+
+/// Scratch of a [`read_ranges_vouched`] call of `nreq` requests in `nseg`
+/// segments ([`read_layout`]).
+pub fn vread_scratch_len(nreq: u64, nseg: u64) -> u64 {
+    unsafe { ffi_vread::chipv_read_scratch_len(nreq, nseg) }
+}
+
+/// [`read_ranges`] with every rebuilt chunk hashed against the CV the stream's
+/// own tree stores for it.  `vouch` (u32 per request, on the device) gets the
+/// OR over the request's segments of [`VOUCHED`], [`UNVOUCHED`] (the path to
+/// the root is damaged too: rebuilt bytes with `read_ranges`' guarantee) and
+/// [`CONTRADICTED`] (the rebuilt chunk does not hash to its stored CV: status
+/// 5, zeros).  With status 0 and no [`UNVOUCHED`] bit every byte handed out is
+/// hashed against the root; with [`VREAD_STRICT`] in `flags` status 0 alone
+/// says so.  Enqueued on `stream`, not synchronised.  Returns the content
+/// length per request.
+#[allow(clippy::too_many_arguments)]
+pub fn read_ranges_vouched(input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer,
+                           padding: &[u32], chunk_len: &[u32], req_stream: &[u32], start: &[u64], len: &[u64],
+                           content: &mut DeviceBuffer, content_off: &[u64], status: &mut DeviceBuffer,
+                           used: &mut DeviceBuffer, vouch: &mut DeviceBuffer, flags: u32, scratch: &mut DeviceBuffer,
+                           stream: Stream) -> Result<Vec<u64>> {
+    let (count, nreq) = (in_len.len(), req_stream.len());
+    if in_off.len() != count || padding.len() != count || chunk_len.len() != count || start.len() != nreq ||
+        len.len() != nreq || content_off.len() != nreq || hashes.len() < count * HASH_LEN ||
+        status.len() < nreq * 4 || used.len() < nreq * 4 || vouch.len() < nreq * 4 ||
+        in_off.iter().zip(in_len).any(|(&o, &l)| o + l > input.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (_, want, _, _) = read_layout(chunk_len, padding, req_stream, start, len, 16)?;
+    if content_off.iter().zip(&want).any(|(&o, &l)| o + l > content.len() as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_vread()?;
+    let mut clen = vec![0u64; nreq];
+    check(unsafe {
+        ffi_vread::chipv_read_ranges_dev(input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), hashes.as_ptr(),
+                                         padding.as_ptr(), chunk_len.as_ptr(), count as u64, req_stream.as_ptr(),
+                                         start.as_ptr(), len.as_ptr(), nreq as u64, content.as_mut_ptr(),
+                                         content_off.as_ptr(), clen.as_mut_ptr(), status.as_mut_ptr() as *mut u32,
+                                         used.as_mut_ptr() as *mut u32, vouch.as_mut_ptr() as *mut u32, flags,
+                                         scratch.ptr, scratch.len() as u64, stream.0)
     })?;
     Ok(clen)
 }

@@ -242,6 +242,17 @@ READ_SIGNATURES = {
                                              ctypes.c_uint64, ctypes.c_void_p]),
 }
 
+# the vread header (include/carbonado_hip_vread.h): ranged reads whose rebuilt
+# chunks are hashed against the stored tree, a sixth table of its own
+VREAD_SIGNATURES = {
+    "chipv_abi_version": (ctypes.c_int, []),
+    "chipv_read_scratch_len": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "chipv_read_ranges_dev": (ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p, c_u32p, c_u32p,
+                                             ctypes.c_uint64, c_u32p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                             c_u64p, c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -263,7 +274,7 @@ def lib() -> ctypes.CDLL:
             pass
         l = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES,
-                                  **READ_SIGNATURES}.items():
+                                  **READ_SIGNATURES, **VREAD_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,84 @@
+// api_vread.cpp — the vouched ranged reads of include/carbonado_hip_vread.h:
+// the ranged reads of api_read.cpp with every rebuilt chunk hashed against the
+// CV stored for it in the stream.  The checks and every table are host code in
+// read_plan.hpp and vread_plan.hpp; this file uploads the table into the
+// caller's scratch and enqueues KA's two checks of the primary slices
+// (audit_kernels.hip, one launch each so that parents and chunks flag
+// different words), the kernels of vread_kernels.hip and KD's read kernel.
+#include "api_common.hpp"
+#include "audit_kernels.hpp"
+#include "vread_kernels.hpp"
+
+using namespace chip;
+using namespace chip::api;
+
+extern "C" {
+
+int chipv_abi_version(void) { return CHIPV_ABI_VERSION; }
+
+uint64_t chipv_read_scratch_len(uint64_t nreq, uint64_t nseg) { return vread::scratch_len(nreq, nseg); }
+
+int chipv_read_ranges_dev(const uint8_t *d_streams, const uint64_t *in_off, const uint64_t *in_len,
+                          const uint8_t *d_hash, const uint32_t *padding, const uint32_t *chunk_len, uint64_t nstreams,
+                          const uint32_t *req_stream, const uint64_t *start, const uint64_t *len, uint64_t nreq,
+                          uint8_t *d_content, const uint64_t *content_off, uint64_t *content_len, uint32_t *d_status,
+                          uint32_t *d_used, uint32_t *d_vouch, uint32_t flags, void *d_scratch, uint64_t scratch_len,
+                          void *stream) {
+    if (nreq == 0) return CHIP_OK;
+    vread::Plan vp;
+    int st = vread::plan_vread(reinterpret_cast<uintptr_t>(d_streams), in_off, in_len,
+                               reinterpret_cast<uintptr_t>(d_hash), padding, chunk_len, nstreams, req_stream, start, len,
+                               nreq, reinterpret_cast<uintptr_t>(d_content), content_off, content_len,
+                               d_status && d_used && d_vouch, flags, reinterpret_cast<uintptr_t>(d_scratch), scratch_len,
+                               &vp);
+    if (st != CHIP_OK) return st;
+    st = use_device();
+    if (st != CHIP_OK) return st;
+    Ctx *c;
+    st = ctx_get(&c);
+    if (st != CHIP_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t *scr = static_cast<uint8_t *>(d_scratch);
+    read::Plan &p = vp.rd;
+    const audit::ScratchLayout &ka = p.ka.lay;
+    CHIP_HIP(h2d(c->stage, scr, p.ka.table.data(), p.ka.table.size(), s));
+    VreadLaunch V{};
+    ReadLaunch &L = V.rd;
+    L.slices = reinterpret_cast<const audit::Req *>(scr + p.lay.audit + ka.reqs);
+    L.parents = reinterpret_cast<const uint64_t *>(scr + p.lay.audit + ka.parents);
+    L.chunks = reinterpret_cast<const uint64_t *>(scr + p.lay.audit + ka.chunks);
+    L.masks = reinterpret_cast<const read::MaskEntry *>(scr + p.lay.masks);
+    L.reqs = reinterpret_cast<const read::Req *>(scr + p.lay.reqs);
+    L.segs = reinterpret_cast<const read::Seg *>(scr + p.lay.segs);
+    L.fpar = reinterpret_cast<const uint64_t *>(scr + p.lay.fpar);
+    L.blocks = reinterpret_cast<const uint64_t *>(scr + p.lay.blocks);
+    L.rstat = reinterpret_cast<uint32_t *>(scr + p.lay.rstat);
+    L.served = reinterpret_cast<read::Served *>(scr + p.lay.served);
+    L.nreq = p.nreq; L.nseg = p.nseg; L.total_blocks = p.total_blocks;
+    L.prim_parents = p.prim_parents; L.prim_chunks = p.prim_chunks; L.fb_parents = p.fb_parents;
+    L.status = d_status; L.used = d_used;
+    V.pathw = reinterpret_cast<uint32_t *>(scr + vp.lay.path);
+    V.contra = reinterpret_cast<uint32_t *>(scr + vp.lay.contra);
+    V.vouch = d_vouch;
+    V.strict = flags & CHIPV_STRICT;
+    if (p.nseg) {
+        CHIP_HIP(hipMemsetAsync(scr + vp.lay.zero_from(), 0, vp.lay.zero_len(), s));
+        AuditLaunch A{};  // KA's checks of every segment's own slice: the parents into the path words,
+        A.reqs = L.slices; A.parents = L.parents; A.chunks = L.chunks; A.units = nullptr;
+        A.nreq = p.nseg; A.total_units = 0;
+        A.proofs = false;
+        A.total_parents = p.prim_parents; A.total_chunks = 0;
+        A.status = V.pathw;
+        CHIP_HIP(audit_verify_launch(A, s));
+        A.total_parents = 0; A.total_chunks = p.prim_chunks;  // the chunks (and the header) into the chunk words
+        A.status = L.rstat;
+        CHIP_HIP(audit_verify_launch(A, s));
+        CHIP_HIP(vread_fallback_launch(V, s));
+        CHIP_HIP(vread_vouch_launch(V, s));
+    }
+    CHIP_HIP(vread_finish_launch(V, s));
+    CHIP_HIP(read_copy_launch(L, s));
+    return CHIP_OK;
+}
+
+}  // extern "C"

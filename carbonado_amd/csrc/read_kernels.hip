@@ -31,6 +31,7 @@
 //    the segment's 4 coefficients as repair_decode_kernel builds its own.  A
 //    request that failed gets zeros over all its segments.
 #include "audit_checks.hpp"
+#include "read_device.hpp"
 #include "read_kernels.hpp"
 #include "zfec_device.hpp"
 
@@ -44,15 +45,6 @@ using audit::QUADS;
 using audit::TPB;
 static_assert(BLOCK == UNIT * TPB, "content bytes per workgroup");
 
-// segment g's own slice request moved to fallback k of its 7 (shard k below its primary p, k + 1 from it on)
-__device__ __forceinline__ audit::Req fallback_slice(audit::Req a, const Seg *segs, uint32_t g, uint32_t k) {
-    const uint32_t p = segs[g].p, spc = segs[g].spc, shard = k < p ? k : k + 1;
-    const uint64_t first = (uint64_t)shard * spc + (a.first - (uint64_t)p * spc);
-    a.last = first + (a.last - a.first);
-    a.first = first;
-    return a;
-}
-
 // items [fpar[g], fpar[g + 1]) are segment g's: 7 x the most parents any of its fallback slices selects
 __global__ __launch_bounds__(TPB) void read_fallback_parent_kernel(const audit::Req *slices, const Seg *segs,
                                                                    const uint64_t *fpar, uint32_t nseg, uint64_t total,
@@ -61,12 +53,7 @@ __global__ __launch_bounds__(TPB) void read_fallback_parent_kernel(const audit::
     if (i >= total) return;
     const uint32_t g = audit::find_req(fpar, nseg, i);
     if (rstat[g] == 0) return;  // the segment's own slice is authentic
-    const uint64_t local = i - fpar[g], each = (fpar[g + 1] - fpar[g]) / FALLBACKS;
-    const uint32_t k = (uint32_t)(local / each);
-    const audit::Req a = fallback_slice(slices[g], segs, g, k);
-    const uint64_t j = local % each;
-    if (j >= audit::sel_parents(a.N, a.first, a.last)) return;  // this slice selects fewer
-    if (!audit::parent_ok<false>(a, j)) flag_mismatch(rstat, nseg + FALLBACKS * g + k);
+    fallback_parent_item(slices, segs, fpar, nseg, i, g, rstat);
 }
 
 // items [7 pre[g], 7 pre[g + 1]) are segment g's, pre = KA's chunk prefix of the primary slices
@@ -79,10 +66,7 @@ __global__ __launch_bounds__(TPB) void read_fallback_chunk_kernel(const audit::R
     if (i >= total) return;  // whole quads leave; the kernel has no workgroup barrier
     const uint32_t g = audit::find_req(pre, nseg, i / FALLBACKS);
     if (rstat[g] == 0) return;
-    const uint64_t local = i - FALLBACKS * pre[g], each = pre[g + 1] - pre[g];
-    const uint32_t k = (uint32_t)(local / each);
-    const audit::Req a = fallback_slice(slices[g], segs, g, k);
-    if (!audit::chunk_ok<false>(a, local % each, msg, t)) flag_mismatch(rstat, nseg + FALLBACKS * g + k);
+    fallback_chunk_item(slices, segs, pre, nseg, i, g, rstat, msg, t);
 }
 
 __global__ __launch_bounds__(TPB) void read_resolve_kernel(const Req *reqs, const Seg *segs, const MaskEntry *masks,
@@ -233,6 +217,11 @@ hipError_t read_serve_launch(const ReadLaunch &L, hipStream_t stream) {
     if (L.nreq)
         hipLaunchKernelGGL(read_resolve_kernel, dim3(nblocks(L.nreq, TPB)), dim3(TPB), 0, stream, L.reqs, L.segs, L.masks,
                            L.rstat, (uint32_t)L.nreq, (uint32_t)L.nseg, L.served, L.status, L.used);
+    return read_copy_launch(L, stream);
+}
+
+hipError_t read_copy_launch(const ReadLaunch &L, hipStream_t stream) {
+    using namespace read;
     if (L.total_blocks)
         hipLaunchKernelGGL(read_kernel, dim3((unsigned)L.total_blocks), dim3(TPB), 0, stream, L.segs, L.blocks,
                            (uint32_t)L.nseg, L.served, L.status);

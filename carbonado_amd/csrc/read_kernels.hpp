@@ -31,4 +31,8 @@ hipError_t read_fallback_launch(const ReadLaunch &L, hipStream_t stream);
 // Enqueue the verdict per request and segment, then the read itself (two launches).
 hipError_t read_serve_launch(const ReadLaunch &L, hipStream_t stream);
 
+// Enqueue the read alone, for a caller that has written `served` and the
+// status words itself (the vouched reads; one launch).
+hipError_t read_copy_launch(const ReadLaunch &L, hipStream_t stream);
+
 }  // namespace chip

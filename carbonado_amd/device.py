@@ -600,6 +600,61 @@ def read_ranges(streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, pad
     return clen[:nreq].tolist()
 
 
+# ---- vouched ranged reads (include/carbonado_hip_vread.h): read_ranges with
+# every rebuilt chunk hashed against the CV the stream's tree stores for it
+
+VOUCHED, UNVOUCHED, CONTRADICTED = 1, 2, 4  # bits of a request's vouch word
+VREAD_STRICT = 1                            # flag: a request with an unvouched segment fails with 7
+
+
+def vread_scratch(nreq: int, nseg: int, device=None) -> torch.Tensor:
+    """Scratch of a read_ranges_vouched call of nreq requests in nseg segments (read_layout)."""
+    size = _lib.lib().chipv_read_scratch_len(nreq, nseg)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def read_ranges_vouched(streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len, req_stream,
+                        start, length, content: torch.Tensor, content_off, status: torch.Tensor, used: torch.Tensor,
+                        vouch: torch.Tensor, scratch: torch.Tensor, flags: int = 0):
+    """read_ranges with the same arguments, layout (read_layout) and bytes,
+    plus a check and its verdict: every chunk of a rebuilt range is rebuilt in
+    full, hashed as that chunk of the stream and compared with the CV its
+    parent stores for it.  vouch int32 / uint32 [nreq] on the device: the OR
+    over the request's segments of VOUCHED (rebuilt, hashes agree), UNVOUCHED
+    (rebuilt, but the path from the chunk's parent to the root is damaged too,
+    so nothing can be compared: read_ranges' guarantee) and CONTRADICTED (the
+    hashes differ).  status: 5 for a request with a contradicted segment
+    (zeros are written), else 7 as read_ranges gives it, and with flags =
+    VREAD_STRICT also for a request with an unvouched segment, else 0.  With
+    status 0 and no UNVOUCHED bit every byte is hashed against the root.
+    status, used and vouch are filled on the device; enqueued on the current
+    stream, not synchronised.  Returns the content length per request."""
+    assert streams.is_cuda and content.is_cuda and hashes.is_cuda and status.is_cuda and used.is_cuda and scratch.is_cuda
+    assert vouch.is_cuda
+    assert streams.dtype == content.dtype == torch.uint8 and streams.dim() == content.dim() == 1
+    assert streams.is_contiguous() and content.is_contiguous() and hashes.is_contiguous()
+    ioff, pioff, nstreams = _arr(in_off)
+    ilen, pilen, nl = _arr(in_len)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    cl, pcl, ncl = _arr(chunk_len, np.uint32)
+    rs, prs, nreq = _arr(req_stream, np.uint32)
+    st, pst, ns = _arr(start)
+    ln, pln, nln = _arr(length)
+    coff, pcoff, nco = _arr(content_off)
+    assert nl == nstreams == npad == ncl and ns == nreq == nln == nco
+    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
+    for t in (status, used, vouch):
+        assert t.numel() >= nreq and t.element_size() == 4 and t.is_contiguous()
+    if nreq and int(rs.max()) < nstreams:  # the content buffer is checked before the call (else: the call reports it)
+        _, want, _, _ = read_layout(cl[:nstreams], pad[:nstreams], rs[:nreq], st[:nreq], ln[:nreq])
+        assert _fits(coff, np.asarray(want, dtype=np.uint64), content.numel())
+    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
+    check(_lib.lib().chipv_read_ranges_dev(_p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams, prs, pst, pln,
+                                           nreq, _p(content), pcoff, clen.ctypes.data_as(_lib.c_u64p), _p(status),
+                                           _p(used), _p(vouch), flags, _p(scratch), scratch.numel(), _stream()))
+    return clen[:nreq].tolist()
+
+
 def host_topology() -> dict:
     """Where this process's host-copy path sits (chip_host_topology): the
     GPU's NUMA node, the calling thread's staging ring node and the copy
