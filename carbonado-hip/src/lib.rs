@@ -26,6 +26,7 @@ mod ffi_audit;
 mod ffi_repair;
 mod ffi_read;
 mod ffi_vread;
+mod ffi_ecies;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -1233,6 +1234,188 @@ pub fn read_ranges_vouched(input: &DeviceBuffer, in_off: &[u64], in_len: &[u64],
                                          scratch.ptr, scratch.len() as u64, stream.0)
     })?;
     Ok(clen)
+}
+
+fn abi_ecies() -> Result<()> {
+    abi()?;
+    match unsafe { ffi_ecies::chipe_abi_version() } {
+        ffi_ecies::CHIPE_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// Status of a message whose tag does not verify ([`gcm_open_ragged`], [`ecies_open_ragged`]).
+pub const ECIES_FAILED: u32 = 17;
+
+/// Scratch of an AES-256-GCM call over messages of `n[o]` bytes.
+pub fn gcm_scratch_len(n: &[u64]) -> u64 {
+    unsafe { ffi_ecies::chipe_gcm_scratch_len(n.as_ptr(), n.len() as u64) }
+}
+
+fn ranges_fit(off: &[u64], len: &[u64], extra: u64, cap: usize) -> bool {
+    off.iter().zip(len).all(|(&o, &l)| o.checked_add(l + extra).map_or(false, |e| e <= cap as u64))
+}
+
+/// AES-256-GCM (16-byte nonce, no AAD) of message o = `input[in_off[o]..][..n[o]]`
+/// (16-B aligned) under `keys[32 o..]` and `ivs[16 o..]`: the ciphertext to
+/// `out[out_off[o]..]` at any byte offset, the tag to `tags[16 o..]`.  A
+/// bitsliced AES and a table-free GHASH on the device, constant time in keys
+/// and plaintext; the key region of the scratch is zeroed by the call's last
+/// operation.  Enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn gcm_seal_ragged(keys: &[u8], ivs: &[u8], input: &DeviceBuffer, in_off: &[u64], n: &[u64],
+                       out: &mut DeviceBuffer, out_off: &[u64], tags: &mut DeviceBuffer, scratch: &mut DeviceBuffer,
+                       stream: Stream) -> Result<()> {
+    let count = n.len();
+    if keys.len() != 32 * count || ivs.len() != 16 * count || in_off.len() != count || out_off.len() != count ||
+        tags.len() < 16 * count || !ranges_fit(in_off, n, 0, input.len()) || !ranges_fit(out_off, n, 0, out.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_ecies()?;
+    check(unsafe {
+        ffi_ecies::chipe_gcm_seal_ragged_dev(keys.as_ptr(), ivs.as_ptr(), input.as_ptr(), in_off.as_ptr(), n.as_ptr(),
+                                             count as u64, out.as_mut_ptr(), out_off.as_ptr(), tags.as_mut_ptr(),
+                                             scratch.ptr, scratch.len() as u64, stream.0)
+    })
+}
+
+/// The reverse of [`gcm_seal_ragged`]: the tags are checked first and the CTR
+/// pass is gated on the verdicts on the device, so a message whose tag fails
+/// gets `status[o]` = [`ECIES_FAILED`] (u32 per message, on the device) and
+/// zeros over its whole range, the others 0 and their plaintext at
+/// `out[out_off[o]..]` (16-B aligned).  Enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn gcm_open_ragged(keys: &[u8], ivs: &[u8], input: &DeviceBuffer, in_off: &[u64], n: &[u64], tags: &DeviceBuffer,
+                       out: &mut DeviceBuffer, out_off: &[u64], status: &mut DeviceBuffer, scratch: &mut DeviceBuffer,
+                       stream: Stream) -> Result<()> {
+    let count = n.len();
+    if keys.len() != 32 * count || ivs.len() != 16 * count || in_off.len() != count || out_off.len() != count ||
+        tags.len() < 16 * count || status.len() < 4 * count || !ranges_fit(in_off, n, 0, input.len()) ||
+        !ranges_fit(out_off, n, 0, out.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_ecies()?;
+    check(unsafe {
+        ffi_ecies::chipe_gcm_open_ragged_dev(keys.as_ptr(), ivs.as_ptr(), input.as_ptr(), in_off.as_ptr(), n.as_ptr(),
+                                             count as u64, tags.as_ptr(), out.as_mut_ptr(), out_off.as_ptr(),
+                                             status.as_mut_ptr() as *mut u32, scratch.ptr, scratch.len() as u64,
+                                             stream.0)
+    })
+}
+
+/// `encoding::ecies` of every resident object to the receiver `pubkey`: the
+/// envelope eph_pub65 || nonce16 || tag16 || ciphertext, `n[o] + 97` bytes, to
+/// `out[out_off[o]..]`.  The key agreement of every object runs on the host
+/// before anything is enqueued; `scratch` holds [`gcm_scratch_len`]`(n)` bytes.
+/// Enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn ecies_seal_ragged(pubkey: &[u8], input: &DeviceBuffer, in_off: &[u64], n: &[u64], out: &mut DeviceBuffer,
+                         out_off: &[u64], scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    let count = n.len();
+    if in_off.len() != count || out_off.len() != count || !ranges_fit(in_off, n, 0, input.len()) ||
+        !ranges_fit(out_off, n, 97, out.len()) || (scratch.len() as u64) < gcm_scratch_len(n) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_ecies()?;
+    check(unsafe {
+        ffi_ecies::chipe_seal_ragged_dev(pubkey.as_ptr(), pubkey.len() as u64, ptr::null(), input.as_ptr(),
+                                         in_off.as_ptr(), n.as_ptr(), count as u64, out.as_mut_ptr(), out_off.as_ptr(),
+                                         scratch.ptr, stream.0)
+    })
+}
+
+/// `decoding::ecies` of every resident envelope `input[in_off[o]..][..in_len[o]]`:
+/// the plaintext to `out[out_off[o]..]` (16-B aligned) and `status[o]` = 0, or
+/// [`ECIES_FAILED`] and zeros.  The call waits once, for the envelopes' header
+/// bytes (the keys depend on them).  Returns the plaintext length per object.
+#[allow(clippy::too_many_arguments)]
+pub fn ecies_open_ragged(secret_key: &[u8], input: &DeviceBuffer, in_off: &[u64], in_len: &[u64],
+                         out: &mut DeviceBuffer, out_off: &[u64], status: &mut DeviceBuffer,
+                         scratch: &mut DeviceBuffer, stream: Stream) -> Result<Vec<u64>> {
+    let count = in_len.len();
+    let plain: Vec<u64> = in_len.iter().map(|&l| l.saturating_sub(97)).collect();
+    if in_off.len() != count || out_off.len() != count || status.len() < 4 * count ||
+        !ranges_fit(in_off, in_len, 0, input.len()) || !ranges_fit(out_off, &plain, 0, out.len()) ||
+        (scratch.len() as u64) < gcm_scratch_len(&plain) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_ecies()?;
+    let mut olen = vec![0u64; count];
+    check(unsafe {
+        ffi_ecies::chipe_open_ragged_dev(secret_key.as_ptr(), secret_key.len() as u64, input.as_ptr(), in_off.as_ptr(),
+                                         in_len.as_ptr(), count as u64, out.as_mut_ptr(), out_off.as_ptr(),
+                                         olen.as_mut_ptr(), status.as_mut_ptr() as *mut u32, scratch.ptr, stream.0)
+    })?;
+    Ok(olen)
+}
+
+/// Scratch of [`encode_ragged_ecies`] (object lengths) / [`decode_ragged_ecies`] (stream lengths).
+pub fn ecies_ragged_scratch_len(format: u8, lens: &[u64], decode: bool) -> u64 {
+    unsafe {
+        if decode {
+            ffi_ecies::chipe_decode_scratch_len(format, lens.as_ptr(), lens.len() as u64)
+        } else {
+            ffi_ecies::chipe_encode_scratch_len(format, lens.as_ptr(), lens.len() as u64)
+        }
+    }
+}
+
+/// encode() at Ecies with Bao and / or Zfec (5, 9, 13) of resident objects in
+/// one call: sealed into envelopes in the scratch, then encoded as
+/// [`encode_ragged`] does at `format & 12` (offsets: [`ragged_layout`] of the
+/// sizes + 97).  Stream bytes, hash and `EncodeInfo` are those of [`encode`].
+#[allow(clippy::too_many_arguments)]
+pub fn encode_ragged_ecies(format: u8, pubkey: &[u8], input: &DeviceBuffer, in_off: &[u64], sizes: &[u64],
+                           out: &mut DeviceBuffer, out_off: &[u64], hashes: &mut DeviceBuffer,
+                           scratch: &mut DeviceBuffer, stream: Stream) -> Result<(Vec<u64>, Vec<ChipEncodeInfo>)> {
+    let count = sizes.len();
+    let env: Vec<u64> = sizes.iter().map(|&n| n + 97).collect();
+    let need_scratch = ecies_ragged_scratch_len(format, sizes, false);
+    if in_off.len() != count || out_off.len() != count || hashes.len() < count * HASH_LEN || need_scratch == 0 ||
+        (scratch.len() as u64) < need_scratch || !ranges_fit(in_off, sizes, 0, input.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (_, need, _) = ragged_layout(format & 12, &env, 256, 0)?;
+    if !ranges_fit(out_off, &need, 0, out.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_ecies()?;
+    let mut lens = vec![0u64; count];
+    let mut infos = vec![ChipEncodeInfo::default(); count];
+    check(unsafe {
+        ffi_ecies::chipe_encode_ragged_dev(format, pubkey.as_ptr(), pubkey.len() as u64, ptr::null(), input.as_ptr(),
+                                           in_off.as_ptr(), sizes.as_ptr(), count as u64, out.as_mut_ptr(),
+                                           out_off.as_ptr(), lens.as_mut_ptr(), hashes.as_mut_ptr(), infos.as_mut_ptr(),
+                                           scratch.ptr, stream.0)
+    })?;
+    Ok((lens, infos))
+}
+
+/// decode() at 5, 9 or 13 of resident streams in one call: [`decode_ragged`] at
+/// `format & 12` into envelopes in the scratch, then [`ecies_open_ragged`]
+/// (which waits once).  `status[o]`: 0, the bao status of a damaged stream (not
+/// opened, zeros) or [`ECIES_FAILED`].  `out` must hold `in_len[o]` bytes from
+/// `out_off[o]`.  Returns the plaintext lengths.
+#[allow(clippy::too_many_arguments)]
+pub fn decode_ragged_ecies(format: u8, secret_key: &[u8], input: &DeviceBuffer, in_off: &[u64], in_len: &[u64],
+                           hashes: &DeviceBuffer, padding: &[u32], out: &mut DeviceBuffer, out_off: &[u64],
+                           status: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream) -> Result<Vec<u64>> {
+    let count = in_len.len();
+    let need_scratch = ecies_ragged_scratch_len(format, in_len, true);
+    if in_off.len() != count || out_off.len() != count || padding.len() != count || hashes.len() < count * HASH_LEN ||
+        status.len() < 4 * count || need_scratch == 0 || (scratch.len() as u64) < need_scratch ||
+        !ranges_fit(in_off, in_len, 0, input.len()) || !ranges_fit(out_off, in_len, 0, out.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_ecies()?;
+    let mut olen = vec![0u64; count];
+    check(unsafe {
+        ffi_ecies::chipe_decode_ragged_dev(format, secret_key.as_ptr(), secret_key.len() as u64, input.as_ptr(),
+                                           in_off.as_ptr(), in_len.as_ptr(), count as u64, hashes.as_ptr(),
+                                           padding.as_ptr(), out.as_mut_ptr(), out_off.as_ptr(), olen.as_mut_ptr(),
+                                           status.as_mut_ptr() as *mut u32, scratch.ptr, stream.0)
+    })?;
+    Ok(olen)
 }
 
 /// encode() of `count` objects in HOST memory, H2D / kernels / D2H and the

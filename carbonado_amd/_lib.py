@@ -253,6 +253,35 @@ VREAD_SIGNATURES = {
                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
 }
 
+# the ecies header (include/carbonado_hip_ecies.h): AES-256-GCM over resident
+# messages, a seventh table of its own
+ECIES_SIGNATURES = {
+    "chipe_abi_version": (ctypes.c_int, []),
+    "chipe_gcm_scratch_len": (ctypes.c_uint64, [c_u64p, ctypes.c_uint64]),
+    "chipe_gcm_seal_ragged_dev": (ctypes.c_int, [c_u8p, c_u8p, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_uint64,
+                                                 ctypes.c_void_p, c_u64p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_uint64, ctypes.c_void_p]),
+    "chipe_gcm_open_ragged_dev": (ctypes.c_int, [c_u8p, c_u8p, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_uint64,
+                                                 ctypes.c_void_p, ctypes.c_void_p, c_u64p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "chipe_seal_ragged_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(EciesInjectC),
+                                             ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                             c_u64p, ctypes.c_void_p, ctypes.c_void_p]),
+    "chipe_open_ragged_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, c_u64p, c_u64p,
+                                             ctypes.c_uint64, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p]),
+    "chipe_encode_scratch_len": (ctypes.c_uint64, [ctypes.c_uint8, c_u64p, ctypes.c_uint64]),
+    "chipe_decode_scratch_len": (ctypes.c_uint64, [ctypes.c_uint8, c_u64p, ctypes.c_uint64]),
+    "chipe_encode_ragged_dev": (ctypes.c_int, [ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.POINTER(EciesInjectC), ctypes.c_void_p, c_u64p, c_u64p,
+                                               ctypes.c_uint64, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p,
+                                               ctypes.POINTER(EncodeInfoC), ctypes.c_void_p, ctypes.c_void_p]),
+    "chipe_decode_ragged_dev": (ctypes.c_int, [ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                               c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p, c_u32p,
+                                               ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -274,7 +303,7 @@ def lib() -> ctypes.CDLL:
             pass
         l = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES,
-                                  **READ_SIGNATURES, **VREAD_SIGNATURES}.items():
+                                  **READ_SIGNATURES, **VREAD_SIGNATURES, **ECIES_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

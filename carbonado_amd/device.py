@@ -655,6 +655,189 @@ def read_ranges_vouched(streams: torch.Tensor, in_off, in_len, hashes: torch.Ten
     return clen[:nreq].tolist()
 
 
+# ---- AES-256-GCM over resident messages (include/carbonado_hip_ecies.h): the
+# data half of the Ecies stage, one ragged batch per call
+
+ECIES_FAILED = 17  # status of a message whose tag does not verify (CHIP_ERR_ECIES)
+
+
+def gcm_scratch(n, device=None) -> torch.Tensor:
+    """Scratch of a gcm_seal_ragged / gcm_open_ragged call over messages of n[o] bytes."""
+    ln, pln, count = _arr(n)
+    size = _lib.lib().chipe_gcm_scratch_len(pln, count)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def _gcm_keys(keys, ivs, count):
+    k = np.frombuffer(bytes(keys), dtype=np.uint8) if not isinstance(keys, np.ndarray) else keys
+    v = np.frombuffer(bytes(ivs), dtype=np.uint8) if not isinstance(ivs, np.ndarray) else ivs
+    k, v = np.ascontiguousarray(k, dtype=np.uint8).reshape(-1), np.ascontiguousarray(v, dtype=np.uint8).reshape(-1)
+    assert k.size == 32 * count and v.size == 16 * count
+    keep_k = k if k.size else np.zeros(1, dtype=np.uint8)
+    keep_v = v if v.size else np.zeros(1, dtype=np.uint8)
+    return keep_k, keep_k.ctypes.data_as(_lib.c_u8p), keep_v, keep_v.ctypes.data_as(_lib.c_u8p)
+
+
+def gcm_seal_ragged(keys, ivs, inp: torch.Tensor, in_off, n, out: torch.Tensor, out_off, tags: torch.Tensor,
+                    scratch: torch.Tensor) -> None:
+    """AES-256-GCM (16-byte nonce, no AAD) of message o = inp[in_off[o] :
+    in_off[o] + n[o]] (16-B aligned) under keys[32 o : 32 o + 32] and
+    ivs[16 o : 16 o + 16] (host bytes): the ciphertext to out[out_off[o] :] at
+    any byte offset, the tag to tags[16 o : 16 o + 16].  Bitsliced AES and a
+    table-free GHASH on the device; the key region of the scratch is zeroed by
+    the call's last operation.  Enqueued on the current stream, not
+    synchronised."""
+    assert inp.is_cuda and out.is_cuda and tags.is_cuda and scratch.is_cuda
+    assert inp.dtype == out.dtype == tags.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ln, pln, nl = _arr(n)
+    ooff, pooff, no = _arr(out_off)
+    assert nl == count == no and tags.numel() >= 16 * count and tags.is_contiguous()
+    assert _fits(ioff, ln[:count], inp.numel()) and _fits(ooff, ln[:count], out.numel())
+    kk, pk, vv, pv = _gcm_keys(keys, ivs, count)
+    check(_lib.lib().chipe_gcm_seal_ragged_dev(pk, pv, _p(inp), pioff, pln, count, _p(out), pooff, _p(tags),
+                                               _p(scratch), scratch.numel(), _stream()))
+
+
+def gcm_open_ragged(keys, ivs, inp: torch.Tensor, in_off, n, tags: torch.Tensor, out: torch.Tensor, out_off,
+                    status: torch.Tensor, scratch: torch.Tensor) -> None:
+    """The reverse: ciphertext o = inp[in_off[o] : in_off[o] + n[o]] (any byte
+    offset) with its tag tags[16 o : 16 o + 16]; the plaintext to
+    out[out_off[o] :] (16-B aligned).  The tags are checked first; the CTR pass
+    is gated on the verdicts on the device, so a message whose tag fails gets
+    status[o] = ECIES_FAILED and zeros over its whole range, the others 0 and
+    their plaintext.  status int32 / uint32 [count] on the device.  Enqueued on
+    the current stream, not synchronised."""
+    assert inp.is_cuda and out.is_cuda and tags.is_cuda and scratch.is_cuda and status.is_cuda
+    assert inp.dtype == out.dtype == tags.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ln, pln, nl = _arr(n)
+    ooff, pooff, no = _arr(out_off)
+    assert nl == count == no and tags.numel() >= 16 * count and tags.is_contiguous()
+    assert status.numel() >= count and status.element_size() == 4 and status.is_contiguous()
+    assert _fits(ioff, ln[:count], inp.numel()) and _fits(ooff, ln[:count], out.numel())
+    kk, pk, vv, pv = _gcm_keys(keys, ivs, count)
+    check(_lib.lib().chipe_gcm_open_ragged_dev(pk, pv, _p(inp), pioff, pln, count, _p(tags), _p(out), pooff,
+                                               _p(status), _p(scratch), scratch.numel(), _stream()))
+
+
+def ecies_seal_ragged(pubkey: bytes, inp: torch.Tensor, in_off, n, out: torch.Tensor, out_off,
+                      scratch: torch.Tensor, inject=None) -> None:
+    """encoding::ecies of every object inp[in_off[o] : in_off[o] + n[o]]
+    (16-B aligned) to the receiver `pubkey` (33 or 65 bytes): the envelope
+    eph_pub65 || nonce16 || tag16 || ciphertext, n[o] + 97 bytes, to
+    out[out_off[o] :].  The key agreement of every object runs on the host
+    before anything is enqueued; the bytes are sealed on the device.  inject:
+    None, or a list of (ephemeral_sk 32 B, nonce 16 B) per object for bit-exact
+    tests.  scratch: gcm_scratch(n).  Enqueued on the current stream, not
+    synchronised."""
+    assert inp.is_cuda and out.is_cuda and scratch.is_cuda and inp.dtype == out.dtype == torch.uint8
+    assert inp.is_contiguous() and out.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ln, pln, nl = _arr(n)
+    ooff, pooff, no = _arr(out_off)
+    assert nl == count == no
+    assert _fits(ioff, ln[:count], inp.numel()) and _fits(ooff, ln[:count] + np.uint64(97), out.numel())
+    assert scratch.numel() >= _lib.lib().chipe_gcm_scratch_len(pln, count)
+    inj, keep = _inject_array(inject, count)
+    check(_lib.lib().chipe_seal_ragged_dev(bytes(pubkey), len(pubkey), inj, _p(inp), pioff, pln, count, _p(out), pooff,
+                                           _p(scratch), _stream()))
+
+
+def ecies_open_ragged(secret_key: bytes, inp: torch.Tensor, in_off, in_len, out: torch.Tensor, out_off,
+                      status: torch.Tensor, scratch: torch.Tensor):
+    """decoding::ecies of every envelope inp[in_off[o] : in_off[o] + in_len[o]]
+    (any byte offset): the plaintext, in_len[o] - 97 bytes, to out[out_off[o] :]
+    (16-B aligned), status[o] = 0; or ECIES_FAILED and zeros for a tag that
+    does not verify, an envelope shorter than 97 bytes or an ephemeral key that
+    does not parse.  The call waits once, for the envelopes' header bytes (the
+    keys depend on them); the rest is enqueued on the current stream.  scratch:
+    gcm_scratch of the plaintext lengths.  Returns the plaintext length per
+    object."""
+    assert inp.is_cuda and out.is_cuda and scratch.is_cuda and status.is_cuda
+    assert inp.dtype == out.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ln, pln, nl = _arr(in_len)
+    ooff, pooff, no = _arr(out_off)
+    assert nl == count == no and _fits(ioff, ln[:count], inp.numel())
+    assert status.numel() >= count and status.element_size() == 4 and status.is_contiguous()
+    plain = np.where(ln[:count] >= 97, ln[:count] - np.uint64(97), np.uint64(0)).astype(np.uint64)
+    assert _fits(ooff, plain, out.numel())
+    pl, ppl, _ = _arr(plain)
+    assert scratch.numel() >= _lib.lib().chipe_gcm_scratch_len(ppl, count)
+    olen = np.zeros(max(count, 1), dtype=np.uint64)
+    check(_lib.lib().chipe_open_ragged_dev(bytes(secret_key), len(secret_key), _p(inp), pioff, pln, count, _p(out),
+                                           pooff, olen.ctypes.data_as(_lib.c_u64p), _p(status), _p(scratch), _stream()))
+    return olen[:count].tolist()
+
+
+def _inject_array(inject, count):
+    if inject is None:
+        return None, []
+    assert len(inject) == count
+    inj, keep = (_lib.EciesInjectC * max(count, 1))(), []
+    for o, (sk, nonce) in enumerate(inject):
+        bs, bn = ctypes.create_string_buffer(bytes(sk), 32), ctypes.create_string_buffer(bytes(nonce), 16)
+        keep += [bs, bn]
+        inj[o].ephemeral_sk, inj[o].nonce = ctypes.addressof(bs), ctypes.addressof(bn)
+    return inj, keep
+
+
+def ecies_ragged_scratch(fmt: int, lens, decode: bool = False, device=None) -> torch.Tensor:
+    """Scratch of encode_ragged_ecies (object lengths) / decode_ragged_ecies (stream lengths)."""
+    ln, pln, count = _arr(lens)
+    fn = _lib.lib().chipe_decode_scratch_len if decode else _lib.lib().chipe_encode_scratch_len
+    return torch.empty(fn(fmt, pln, count), dtype=torch.uint8, device=device or "cuda")
+
+
+def encode_ragged_ecies(fmt: int, pubkey: bytes, inp: torch.Tensor, in_off, sizes, out: torch.Tensor, out_off,
+                        hashes: torch.Tensor, scratch: torch.Tensor, inject=None):
+    """encode() at Ecies with Bao and / or Zfec (5, 9, 13) of resident objects
+    in one call: sealed into envelopes in the scratch, then encoded as
+    encode_ragged does at fmt & 12 (offsets: ragged_layout(fmt & 12, sizes +
+    97)).  Stream bytes, hash and EncodeInfo are those of encode() at fmt.
+    Returns (encoded length per object, EncodeInfo per object)."""
+    from .structs import EncodeInfo
+    assert inp.is_cuda and out.is_cuda and hashes.is_cuda and scratch.is_cuda
+    assert inp.dtype == out.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ln, pln, nl = _arr(sizes)
+    ooff, pooff, no = _arr(out_off)
+    assert nl == count == no and hashes.numel() >= 32 * count and hashes.is_contiguous()
+    assert _fits(ioff, ln[:count], inp.numel())
+    assert scratch.numel() >= _lib.lib().chipe_encode_scratch_len(fmt, pln, count)
+    inj, keep = _inject_array(inject, count)
+    olen = (ctypes.c_uint64 * max(count, 1))()
+    info = (_lib.EncodeInfoC * max(count, 1))()
+    check(_lib.lib().chipe_encode_ragged_dev(fmt, bytes(pubkey), len(pubkey), inj, _p(inp), pioff, pln, count, _p(out),
+                                             pooff, olen, _p(hashes), info, _p(scratch), _stream()))
+    assert all(int(a) + b <= out.numel() for a, b in zip(ooff[:count], list(olen)[:count]))
+    return list(olen)[:count], [EncodeInfo.from_c(info[o]) for o in range(count)]
+
+
+def decode_ragged_ecies(fmt: int, secret_key: bytes, enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding,
+                        out: torch.Tensor, out_off, status: torch.Tensor, scratch: torch.Tensor):
+    """decode() at 5, 9 or 13 of resident streams in one call: decode_ragged at
+    fmt & 12 into envelopes in the scratch, then ecies_open_ragged.  status[o]:
+    0, the bao status of a damaged stream (not opened, zeros), or ECIES_FAILED.
+    Returns the plaintext length per object."""
+    assert enc.is_cuda and out.is_cuda and status.is_cuda and scratch.is_cuda
+    assert enc.dtype == out.dtype == torch.uint8 and enc.is_contiguous() and out.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ln, pln, nl = _arr(in_len)
+    ooff, pooff, no = _arr(out_off)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    assert nl == count == no == npad and _fits(ioff, ln[:count], enc.numel())
+    assert status.numel() >= count and status.element_size() == 4 and status.is_contiguous()
+    assert scratch.numel() >= _lib.lib().chipe_decode_scratch_len(fmt, pln, count)
+    olen = np.zeros(max(count, 1), dtype=np.uint64)
+    check(_lib.lib().chipe_decode_ragged_dev(fmt, bytes(secret_key), len(secret_key), _p(enc), pioff, pln, count,
+                                             _p(hashes) if hashes is not None else None, ppad, _p(out), pooff,
+                                             olen.ctypes.data_as(_lib.c_u64p), _p(status), _p(scratch), _stream()))
+    assert _fits(ooff, olen[:count], out.numel())
+    return olen[:count].tolist()
+
+
 def host_topology() -> dict:
     """Where this process's host-copy path sits (chip_host_topology): the
     GPU's NUMA node, the calling thread's staging ring node and the copy
