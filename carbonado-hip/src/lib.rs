@@ -27,6 +27,7 @@ mod ffi_repair;
 mod ffi_read;
 mod ffi_vread;
 mod ffi_ecies;
+mod ffi_snap;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -1416,6 +1417,170 @@ pub fn decode_ragged_ecies(format: u8, secret_key: &[u8], input: &DeviceBuffer, 
                                            status.as_mut_ptr() as *mut u32, scratch.ptr, stream.0)
     })?;
     Ok(olen)
+}
+
+fn abi_snap() -> Result<()> {
+    abi()?;
+    match unsafe { ffi_snap::chips_abi_version() } {
+        ffi_snap::CHIPS_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// Status of a stream that is no valid frame stream ([`unsnap_ragged`], [`decode_ragged_snap`]).
+pub const SNAP_FAILED: u32 = 16;
+
+/// Scratch of [`snap_ragged`] over objects of `n[o]` bytes (`out_cap` = None),
+/// or of [`unsnap_ragged`] over streams of `n[o]` bytes into these capacities.
+pub fn snap_scratch(n: &[u64], out_cap: Option<&[u64]>) -> u64 {
+    unsafe {
+        match out_cap {
+            None => ffi_snap::chips_snap_scratch_len(n.as_ptr(), n.len() as u64),
+            Some(cap) if cap.len() == n.len() => {
+                ffi_snap::chips_unsnap_scratch_len(n.as_ptr(), cap.as_ptr(), n.len() as u64)
+            }
+            Some(_) => 0,
+        }
+    }
+}
+
+/// `encoding::snap` of every resident object `input[in_off[o]..][..n[o]]`
+/// (16-B aligned): its frame stream, bit-exact with [`snap_compress`], to
+/// `out[out_off[o]..]` at any byte offset (capacity `chip_snap_max_len(n[o])`),
+/// its length to `out_len[o]` (u64 per object, on the device).  Enqueued on
+/// `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn snap_ragged(input: &DeviceBuffer, in_off: &[u64], n: &[u64], out: &mut DeviceBuffer, out_off: &[u64],
+                   out_len: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    let count = n.len();
+    let worst: Vec<u64> = n.iter().map(|&x| unsafe { ffi::chip_snap_max_len(x) }).collect();
+    if in_off.len() != count || out_off.len() != count || out_len.len() < 8 * count ||
+        !ranges_fit(in_off, n, 0, input.len()) || !ranges_fit(out_off, &worst, 0, out.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_snap()?;
+    check(unsafe {
+        ffi_snap::chips_snap_ragged_dev(input.as_ptr(), in_off.as_ptr(), n.as_ptr(), count as u64, out.as_mut_ptr(),
+                                        out_off.as_ptr(), out_len.as_mut_ptr() as *mut u64, scratch.ptr,
+                                        scratch.len() as u64, stream.0)
+    })
+}
+
+/// `decoding::snap` of every resident frame stream `input[in_off[o]..][..in_len[o]]`
+/// (any byte offset) into `out[out_off[o]..]` (16-B aligned, capacity
+/// `out_cap[o]`): `status[o]` (u32) and `out_len[o]` (u64), both on the device,
+/// are what [`snap_decompress`] gives.  A stream that fails leaves no
+/// decompressed byte.  Enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn unsnap_ragged(input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], out: &mut DeviceBuffer, out_off: &[u64],
+                     out_cap: &[u64], out_len: &mut DeviceBuffer, status: &mut DeviceBuffer,
+                     scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    let count = in_len.len();
+    if in_off.len() != count || out_off.len() != count || out_cap.len() != count || out_len.len() < 8 * count ||
+        status.len() < 4 * count || !ranges_fit(in_off, in_len, 0, input.len()) ||
+        !ranges_fit(out_off, out_cap, 0, out.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_snap()?;
+    check(unsafe {
+        ffi_snap::chips_unsnap_ragged_dev(input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), count as u64,
+                                          out.as_mut_ptr(), out_off.as_ptr(), out_cap.as_ptr(),
+                                          out_len.as_mut_ptr() as *mut u64, status.as_mut_ptr() as *mut u32,
+                                          scratch.ptr, scratch.len() as u64, stream.0)
+    })
+}
+
+/// Where [`encode_ragged_snap`]'s caller should put each object: [`ragged_layout`]
+/// over the worst-case lengths, since the encoded length depends on the data.
+/// Returns (out_off, out_cap, total).
+pub fn snap_encode_layout(format: u8, sizes: &[u64], align: u64, stream_offset: u64)
+                          -> Result<(Vec<u64>, Vec<u64>, u64)> {
+    let mut off = vec![0u64; sizes.len()];
+    let mut cap = vec![0u64; sizes.len()];
+    let mut total = 0u64;
+    check(unsafe {
+        ffi_snap::chips_encode_layout(format, sizes.as_ptr(), sizes.len() as u64, align, stream_offset,
+                                      off.as_mut_ptr(), cap.as_mut_ptr(), &mut total)
+    })?;
+    Ok((off, cap, total))
+}
+
+/// Scratch of [`encode_ragged_snap`] (object lengths, `out_cap` = None) or of
+/// [`decode_ragged_snap`] (stream lengths and output capacities).
+pub fn snap_ragged_scratch(format: u8, lens: &[u64], out_cap: Option<&[u64]>) -> u64 {
+    unsafe {
+        match out_cap {
+            None => ffi_snap::chips_encode_scratch_len(format, lens.as_ptr(), lens.len() as u64),
+            Some(cap) if cap.len() == lens.len() => {
+                ffi_snap::chips_decode_scratch_len(format, lens.as_ptr(), cap.as_ptr(), lens.len() as u64)
+            }
+            Some(_) => 0,
+        }
+    }
+}
+
+/// encode() at a format with the Snappy bit and Bao and / or Zfec (6, 7, 10,
+/// 11, 14, 15) of resident objects in one call: compressed into rows of the
+/// scratch, then (sealed to `pubkey` with the Ecies bit and) encoded as
+/// [`encode_ragged`] does at `format & 12` (offsets: [`snap_encode_layout`]).
+/// The call waits once, for the compressed lengths.  Stream bytes, hash and
+/// `EncodeInfo` are those of [`encode`].
+#[allow(clippy::too_many_arguments)]
+pub fn encode_ragged_snap(format: u8, pubkey: &[u8], input: &DeviceBuffer, in_off: &[u64], sizes: &[u64],
+                          out: &mut DeviceBuffer, out_off: &[u64], hashes: &mut DeviceBuffer,
+                          scratch: &mut DeviceBuffer, stream: Stream) -> Result<(Vec<u64>, Vec<ChipEncodeInfo>)> {
+    let count = sizes.len();
+    let need_scratch = snap_ragged_scratch(format, sizes, None);
+    if in_off.len() != count || out_off.len() != count || hashes.len() < count * HASH_LEN || need_scratch == 0 ||
+        (scratch.len() as u64) < need_scratch || !ranges_fit(in_off, sizes, 0, input.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (_, cap, _) = snap_encode_layout(format, sizes, 256, 0)?;
+    if !ranges_fit(out_off, &cap, 0, out.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_snap()?;
+    let mut lens = vec![0u64; count];
+    let mut infos = vec![ChipEncodeInfo::default(); count];
+    let pk = if pubkey.is_empty() { ptr::null() } else { pubkey.as_ptr() };
+    check(unsafe {
+        ffi_snap::chips_encode_ragged_dev(format, pk, pubkey.len() as u64, ptr::null(), input.as_ptr(),
+                                          in_off.as_ptr(), sizes.as_ptr(), count as u64, out.as_mut_ptr(),
+                                          out_off.as_ptr(), lens.as_mut_ptr(), hashes.as_mut_ptr(), infos.as_mut_ptr(),
+                                          scratch.ptr, stream.0)
+    })?;
+    Ok((lens, infos))
+}
+
+/// decode() at 6, 7, 10, 11, 14 or 15 of resident streams in one call:
+/// [`decode_ragged`] (or [`decode_ragged_ecies`]) into rows of the scratch, then
+/// [`unsnap_ragged`] into `out[out_off[o]..]` (capacity `out_cap[o]`).
+/// `status[o]` (u32, on the device): 0, the bao / ecies status of an object
+/// that failed there (not decompressed, nothing written) or a snappy status;
+/// `out_len[o]` (u64, on the device): the decoded length.  Without the Ecies
+/// bit nothing is waited for.
+#[allow(clippy::too_many_arguments)]
+pub fn decode_ragged_snap(format: u8, secret_key: &[u8], input: &DeviceBuffer, in_off: &[u64], in_len: &[u64],
+                          hashes: &DeviceBuffer, padding: &[u32], out: &mut DeviceBuffer, out_off: &[u64],
+                          out_cap: &[u64], out_len: &mut DeviceBuffer, status: &mut DeviceBuffer,
+                          scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    let count = in_len.len();
+    let need_scratch = snap_ragged_scratch(format, in_len, Some(out_cap));
+    if in_off.len() != count || out_off.len() != count || out_cap.len() != count || padding.len() != count ||
+        hashes.len() < count * HASH_LEN || status.len() < 4 * count || out_len.len() < 8 * count ||
+        need_scratch == 0 || (scratch.len() as u64) < need_scratch || !ranges_fit(in_off, in_len, 0, input.len()) ||
+        !ranges_fit(out_off, out_cap, 0, out.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_snap()?;
+    let sk = if secret_key.is_empty() { ptr::null() } else { secret_key.as_ptr() };
+    check(unsafe {
+        ffi_snap::chips_decode_ragged_dev(format, sk, secret_key.len() as u64, input.as_ptr(), in_off.as_ptr(),
+                                          in_len.as_ptr(), count as u64, hashes.as_ptr(), padding.as_ptr(),
+                                          out.as_mut_ptr(), out_off.as_ptr(), out_cap.as_ptr(),
+                                          out_len.as_mut_ptr() as *mut u64, status.as_mut_ptr() as *mut u32,
+                                          scratch.ptr, stream.0)
+    })
 }
 
 /// encode() of `count` objects in HOST memory, H2D / kernels / D2H and the

@@ -282,6 +282,33 @@ ECIES_SIGNATURES = {
                                                ctypes.c_void_p]),
 }
 
+# the snap header (include/carbonado_hip_snap.h): the snappy framing format over
+# resident objects and the one-call forms of the levels with the Snappy bit, an
+# eighth table of its own
+SNAP_SIGNATURES = {
+    "chips_abi_version": (ctypes.c_int, []),
+    "chips_snap_scratch_len": (ctypes.c_uint64, [c_u64p, ctypes.c_uint64]),
+    "chips_unsnap_scratch_len": (ctypes.c_uint64, [c_u64p, c_u64p, ctypes.c_uint64]),
+    "chips_snap_ragged_dev": (ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                             c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.c_void_p]),
+    "chips_unsnap_ragged_dev": (ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                               c_u64p, c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_uint64, ctypes.c_void_p]),
+    "chips_encode_layout": (ctypes.c_int, [ctypes.c_uint8, c_u64p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                           c_u64p, c_u64p, c_u64p]),
+    "chips_encode_scratch_len": (ctypes.c_uint64, [ctypes.c_uint8, c_u64p, ctypes.c_uint64]),
+    "chips_decode_scratch_len": (ctypes.c_uint64, [ctypes.c_uint8, c_u64p, c_u64p, ctypes.c_uint64]),
+    "chips_encode_ragged_dev": (ctypes.c_int, [ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.POINTER(EciesInjectC), ctypes.c_void_p, c_u64p, c_u64p,
+                                               ctypes.c_uint64, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p,
+                                               ctypes.POINTER(EncodeInfoC), ctypes.c_void_p, ctypes.c_void_p]),
+    "chips_decode_ragged_dev": (ctypes.c_int, [ctypes.c_uint8, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                               c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p, c_u32p,
+                                               ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -303,7 +330,8 @@ def lib() -> ctypes.CDLL:
             pass
         l = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES,
-                                  **READ_SIGNATURES, **VREAD_SIGNATURES, **ECIES_SIGNATURES}.items():
+                                  **READ_SIGNATURES, **VREAD_SIGNATURES, **ECIES_SIGNATURES,
+                                  **SNAP_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

@@ -838,6 +838,152 @@ def decode_ragged_ecies(fmt: int, secret_key: bytes, enc: torch.Tensor, in_off, 
     return olen[:count].tolist()
 
 
+# ---- snappy on the device (include/carbonado_hip_snap.h): the framing format
+# of encoding::snap / decoding::snap over ragged batches, bit-exact with
+# chip_snap_compress, and the one-call forms of formats 6, 7, 10, 11, 14, 15
+
+SNAP_FAILED = 16        # status of a stream that is not a valid frame stream (CHIP_ERR_SNAP)
+SNAP_TOO_SMALL = 2      # its content does not fit the capacity (CHIP_ERR_BUFFER_TOO_SMALL)
+SNAP_TOO_MANY = 11      # more data chunks than the capacity's slots (CHIP_ERR_UNSUPPORTED_FORMAT)
+
+
+def snap_max_len(n: int) -> int:
+    return int(_lib.lib().chip_snap_max_len(int(n)))
+
+
+def snap_scratch(n, out_cap=None, device=None) -> torch.Tensor:
+    """Scratch of a snap_ragged call over objects of n[o] bytes, or (with
+    out_cap) of an unsnap_ragged call over streams of n[o] bytes."""
+    ln, pln, count = _arr(n)
+    if out_cap is None:
+        size = _lib.lib().chips_snap_scratch_len(pln, count)
+    else:
+        cap, pcap, _ = _arr(out_cap)
+        size = _lib.lib().chips_unsnap_scratch_len(pln, pcap, count)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def snap_ragged(inp: torch.Tensor, in_off, n, out: torch.Tensor, out_off, out_len: torch.Tensor,
+                scratch: torch.Tensor) -> None:
+    """encoding::snap of every object inp[in_off[o] : in_off[o] + n[o]] (16-B
+    aligned): its frame stream, the bytes chip_snap_compress gives, to
+    out[out_off[o] :] at any byte offset (capacity snap_max_len(n[o])), its
+    length to out_len[o] (int64 [count] on the device).  Enqueued on the
+    current stream, not synchronised."""
+    assert inp.is_cuda and out.is_cuda and out_len.is_cuda and scratch.is_cuda
+    assert inp.dtype == out.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ln, pln, nl = _arr(n)
+    ooff, pooff, no = _arr(out_off)
+    assert nl == count == no and out_len.numel() >= count and out_len.element_size() == 8 and out_len.is_contiguous()
+    worst = np.array([snap_max_len(x) for x in ln[:count]], dtype=np.uint64)
+    assert _fits(ioff, ln[:count], inp.numel()) and _fits(ooff, worst, out.numel())
+    check(_lib.lib().chips_snap_ragged_dev(_p(inp), pioff, pln, count, _p(out), pooff, _p(out_len), _p(scratch),
+                                           scratch.numel(), _stream()))
+
+
+def unsnap_ragged(inp: torch.Tensor, in_off, in_len, out: torch.Tensor, out_off, out_cap, out_len: torch.Tensor,
+                  status: torch.Tensor, scratch: torch.Tensor) -> None:
+    """decoding::snap of every frame stream inp[in_off[o] : in_off[o] +
+    in_len[o]] (any byte offset) into out[out_off[o] :] (16-B aligned, capacity
+    out_cap[o]); status[o] (int32 / uint32) and out_len[o] (int64) on the
+    device are what chip_snap_decompress gives.  A stream that fails leaves no
+    decompressed byte: untouched for a framing error or a small capacity, zeros
+    for a block that does not decode or whose CRC disagrees.  Enqueued on the
+    current stream, not synchronised."""
+    assert inp.is_cuda and out.is_cuda and out_len.is_cuda and status.is_cuda and scratch.is_cuda
+    assert inp.dtype == out.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ln, pln, nl = _arr(in_len)
+    ooff, pooff, no = _arr(out_off)
+    cap, pcap, nc = _arr(out_cap)
+    assert nl == count == no == nc
+    assert out_len.numel() >= count and out_len.element_size() == 8 and out_len.is_contiguous()
+    assert status.numel() >= count and status.element_size() == 4 and status.is_contiguous()
+    assert _fits(ioff, ln[:count], inp.numel()) and _fits(ooff, cap[:count], out.numel())
+    check(_lib.lib().chips_unsnap_ragged_dev(_p(inp), pioff, pln, count, _p(out), pooff, pcap, _p(out_len), _p(status),
+                                             _p(scratch), scratch.numel(), _stream()))
+
+
+def snap_encode_layout(fmt: int, sizes, align: int = 256, stream_offset: int = STREAM_OFFSET):
+    """Where encode_ragged_snap's caller should put each object (host only):
+    ragged_layout over the worst-case lengths, since the encoded length depends
+    on the data.  Returns (out_off, out_cap, total)."""
+    n, pn, count = _arr(sizes)
+    off, cap = np.zeros(max(count, 1), dtype=np.uint64), np.zeros(max(count, 1), dtype=np.uint64)
+    total = ctypes.c_uint64()
+    check(_lib.lib().chips_encode_layout(fmt, pn, count, align, stream_offset, off.ctypes.data_as(_lib.c_u64p),
+                                         cap.ctypes.data_as(_lib.c_u64p), ctypes.byref(total)))
+    return off[:count].tolist(), cap[:count].tolist(), total.value
+
+
+def snap_ragged_scratch(fmt: int, lens, out_cap=None, device=None) -> torch.Tensor:
+    """Scratch of encode_ragged_snap (object lengths) or, with out_cap, of
+    decode_ragged_snap (stream lengths and output capacities)."""
+    ln, pln, count = _arr(lens)
+    if out_cap is None:
+        size = _lib.lib().chips_encode_scratch_len(fmt, pln, count)
+    else:
+        cap, pcap, _ = _arr(out_cap)
+        size = _lib.lib().chips_decode_scratch_len(fmt, pln, pcap, count)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def encode_ragged_snap(fmt: int, inp: torch.Tensor, in_off, sizes, out: torch.Tensor, out_off, hashes: torch.Tensor,
+                       scratch: torch.Tensor, pubkey: bytes = None, inject=None):
+    """encode() at a format with the Snappy bit and Bao and / or Zfec (6, 7,
+    10, 11, 14, 15) of resident objects in one call: compressed into rows of
+    the scratch, then (sealed and) encoded as encode_ragged does at fmt & 12.
+    The call waits once, for the compressed lengths.  Offsets:
+    snap_encode_layout(fmt, sizes).  Stream bytes, hash and EncodeInfo are
+    those of encode() at fmt.  Returns (encoded length per object, EncodeInfo
+    per object)."""
+    from .structs import EncodeInfo
+    assert inp.is_cuda and out.is_cuda and hashes.is_cuda and scratch.is_cuda
+    assert inp.dtype == out.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ln, pln, nl = _arr(sizes)
+    ooff, pooff, no = _arr(out_off)
+    assert nl == count == no and hashes.numel() >= 32 * count and hashes.is_contiguous()
+    assert _fits(ioff, ln[:count], inp.numel())
+    assert scratch.numel() >= _lib.lib().chips_encode_scratch_len(fmt, pln, count)
+    inj, keep = _inject_array(inject, count)
+    olen = (ctypes.c_uint64 * max(count, 1))()
+    info = (_lib.EncodeInfoC * max(count, 1))()
+    pk = bytes(pubkey) if pubkey is not None else None
+    check(_lib.lib().chips_encode_ragged_dev(fmt, pk, len(pk) if pk else 0, inj, _p(inp), pioff, pln, count, _p(out),
+                                             pooff, olen, _p(hashes), info, _p(scratch), _stream()))
+    assert all(int(a) + b <= out.numel() for a, b in zip(ooff[:count], list(olen)[:count]))
+    return list(olen)[:count], [EncodeInfo.from_c(info[o]) for o in range(count)]
+
+
+def decode_ragged_snap(fmt: int, enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, out: torch.Tensor,
+                       out_off, out_cap, out_len: torch.Tensor, status: torch.Tensor, scratch: torch.Tensor,
+                       secret_key: bytes = None) -> None:
+    """decode() at 6, 7, 10, 11, 14 or 15 of resident streams in one call:
+    decode_ragged (or decode_ragged_ecies) into rows of the scratch, then
+    unsnap_ragged into out[out_off[o] :] (capacity out_cap[o]).  status[o]: 0,
+    the bao / ecies status of an object that failed there (not decompressed,
+    nothing written), or a snappy status; out_len[o] (int64 on the device): the
+    decoded length.  Without the Ecies bit nothing is waited for."""
+    assert enc.is_cuda and out.is_cuda and status.is_cuda and scratch.is_cuda and out_len.is_cuda
+    assert enc.dtype == out.dtype == torch.uint8 and enc.is_contiguous() and out.is_contiguous()
+    ioff, pioff, count = _arr(in_off)
+    ln, pln, nl = _arr(in_len)
+    ooff, pooff, no = _arr(out_off)
+    cap, pcap, nc = _arr(out_cap)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    assert nl == count == no == npad == nc and _fits(ioff, ln[:count], enc.numel())
+    assert _fits(ooff, cap[:count], out.numel())
+    assert status.numel() >= count and status.element_size() == 4 and status.is_contiguous()
+    assert out_len.numel() >= count and out_len.element_size() == 8 and out_len.is_contiguous()
+    assert scratch.numel() >= _lib.lib().chips_decode_scratch_len(fmt, pln, pcap, count)
+    sk = bytes(secret_key) if secret_key is not None else None
+    check(_lib.lib().chips_decode_ragged_dev(fmt, sk, len(sk) if sk else 0, _p(enc), pioff, pln, count,
+                                             _p(hashes) if hashes is not None else None, ppad, _p(out), pooff, pcap,
+                                             _p(out_len), _p(status), _p(scratch), _stream()))
+
+
 def host_topology() -> dict:
     """Where this process's host-copy path sits (chip_host_topology): the
     GPU's NUMA node, the calling thread's staging ring node and the copy
