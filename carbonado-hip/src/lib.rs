@@ -28,6 +28,7 @@ mod ffi_read;
 mod ffi_vread;
 mod ffi_ecies;
 mod ffi_snap;
+mod ffi_cread;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -1640,6 +1641,143 @@ pub fn decode_host_batch(format: u8, secret_key: &[u8], hashes: &[u8], input: &[
         .zip(lens)
         .map(|(s, l)| if s == ffi::CHIP_OK { Ok(l) } else { Err(ChipError::from_status(s, HASH_LEN, l)) })
         .collect())
+}
+
+fn abi_cread() -> Result<()> {
+    abi_vread()?;
+    abi_ecies()?;
+    match unsafe { ffi_cread::chipc_abi_version() } {
+        ffi_cread::CHIPC_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// Scratch of a [`ctr_ranges`] call over `nitems` items under `nkeys` keys.
+pub fn ctr_scratch(nkeys: u64, nitems: u64) -> u64 {
+    unsafe { ffi_cread::chipc_ctr_scratch_len(nkeys, nitems) }
+}
+
+/// Item i XORs `buf[buf_off[i]..][..n[i]]` (16-B aligned) in place with
+/// keystream bytes `[pos[i], pos[i] + n[i])` of AES-256-GCM (16-byte nonce)
+/// under `keys[32 k..]` and `ivs[16 k..]`, k = `item_key[i]`.  The same call
+/// encrypts and decrypts.  `gate`: u32 per item on the device; item i is
+/// skipped where its word is not zero.  Constant time in keys and keystream;
+/// the key region of the scratch is zeroed by the call's last operation.
+/// Enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn ctr_ranges(keys: &[u8], ivs: &[u8], item_key: &[u32], pos: &[u64], n: &[u64], buf: &mut DeviceBuffer,
+                  buf_off: &[u64], gate: Option<&DeviceBuffer>, scratch: &mut DeviceBuffer, stream: Stream)
+                  -> Result<()> {
+    let (nkeys, nitems) = (keys.len() / 32, n.len());
+    if keys.len() != 32 * nkeys || ivs.len() != 16 * nkeys || item_key.len() != nitems || pos.len() != nitems ||
+        buf_off.len() != nitems || !ranges_fit(buf_off, n, 0, buf.len()) ||
+        gate.map_or(false, |g| g.len() < 4 * nitems) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_cread()?;
+    check(unsafe {
+        ffi_cread::chipc_ctr_ranges_dev(keys.as_ptr(), ivs.as_ptr(), nkeys as u64, item_key.as_ptr(), pos.as_ptr(),
+                                        n.as_ptr(), nitems as u64, buf.as_mut_ptr(), buf_off.as_ptr(),
+                                        gate.map_or(std::ptr::null(), |g| g.as_ptr() as *const u32), scratch.ptr,
+                                        scratch.len() as u64, stream.0)
+    })
+}
+
+/// Scratch of a [`stream_keys`] call over `nstreams` streams.
+pub fn stream_keys_scratch(nstreams: u64) -> u64 {
+    unsafe { ffi_cread::chipc_stream_keys_scratch_len(nstreams) }
+}
+
+/// The AES key and nonce of every resident level-13 stream: envelope bytes
+/// `[0, 81)` read by a strict vouched read (so only bytes hashed against the
+/// root), one key agreement per stream on the host.  The call waits once, for
+/// the header bytes.  Returns (keys, 32 bytes per stream; nonces, 16 bytes per
+/// stream; key status per stream: 0, 5 or 7 for a header that cannot be served,
+/// 17 for an object shorter than 97 bytes or an ephemeral key that does not
+/// parse, with zeros for key and nonce).  The keys are the caller's to wipe.
+#[allow(clippy::too_many_arguments)]
+pub fn stream_keys(secret_key: &[u8], input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer,
+                   padding: &[u32], chunk_len: &[u32], scratch: &mut DeviceBuffer, stream: Stream)
+                   -> Result<(Vec<u8>, Vec<u8>, Vec<u32>)> {
+    let count = in_len.len();
+    if in_off.len() != count || padding.len() != count || chunk_len.len() != count ||
+        hashes.len() < count * HASH_LEN || !ranges_fit(in_off, in_len, 0, input.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_cread()?;
+    let (mut keys, mut ivs, mut status) = (vec![0u8; 32 * count], vec![0u8; 16 * count], vec![0u32; count]);
+    check(unsafe {
+        ffi_cread::chipc_stream_keys_dev(secret_key.as_ptr(), secret_key.len() as u64, input.as_ptr(), in_off.as_ptr(),
+                                         in_len.as_ptr(), hashes.as_ptr(), padding.as_ptr(), chunk_len.as_ptr(),
+                                         count as u64, keys.as_mut_ptr(), ivs.as_mut_ptr(), status.as_mut_ptr(),
+                                         scratch.ptr, scratch.len() as u64, stream.0)
+    })?;
+    Ok((keys, ivs, status))
+}
+
+/// [`read_layout`] for requests in plaintext bytes of level-13 streams:
+/// plaintext `[start, min(P, start + len))` with P = 4 chunk_len - padding - 97.
+pub fn plain_read_layout(chunk_len: &[u32], padding: &[u32], req_stream: &[u32], start: &[u64], len: &[u64],
+                         align: u64) -> Result<(Vec<u64>, Vec<u64>, u64, u64)> {
+    let nreq = req_stream.len();
+    if padding.len() != chunk_len.len() || start.len() != nreq || len.len() != nreq {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (mut off, mut clen, mut total, mut nseg) = (vec![0u64; nreq], vec![0u64; nreq], 0u64, 0u64);
+    check(unsafe {
+        ffi_cread::chipc_read_layout(chunk_len.as_ptr(), padding.as_ptr(), chunk_len.len() as u64,
+                                     req_stream.as_ptr(), start.as_ptr(), len.as_ptr(), nreq as u64, align,
+                                     off.as_mut_ptr(), clen.as_mut_ptr(), &mut total, &mut nseg)
+    })?;
+    Ok((off, clen, total, nseg))
+}
+
+/// Scratch of a [`read_plain_ranges`] call of `nreq` requests in `nseg`
+/// segments ([`plain_read_layout`]) over `nstreams` streams.
+pub fn plain_read_scratch(nreq: u64, nseg: u64, nstreams: u64) -> u64 {
+    unsafe { ffi_cread::chipc_read_scratch_len(nreq, nseg, nstreams) }
+}
+
+/// Plaintext bytes `[start[r], start[r] + len[r])` of resident level-13 stream
+/// `req_stream[r]` into `content[content_off[r]..]`, with `keys`, `ivs` and
+/// `key_status` as [`stream_keys`] gave them: [`read_ranges_vouched`] of the
+/// envelope bytes behind the range, then the keystream taken off in place,
+/// gated on the read's status.  A request whose stream has a non-zero key
+/// status gets that status, zeros, used 0 and vouch 0.  The GCM tag is NOT
+/// checked: the ciphertext is vouched for by the root hash, and a wrong key
+/// gives status 0 and bytes that are not the plaintext.  Enqueued on `stream`,
+/// not synchronised.  Returns the content length per request.
+#[allow(clippy::too_many_arguments)]
+pub fn read_plain_ranges(keys: &[u8], ivs: &[u8], key_status: Option<&[u32]>, input: &DeviceBuffer, in_off: &[u64],
+                         in_len: &[u64], hashes: &DeviceBuffer, padding: &[u32], chunk_len: &[u32],
+                         req_stream: &[u32], start: &[u64], len: &[u64], content: &mut DeviceBuffer,
+                         content_off: &[u64], status: &mut DeviceBuffer, used: &mut DeviceBuffer,
+                         vouch: &mut DeviceBuffer, flags: u32, scratch: &mut DeviceBuffer, stream: Stream)
+                         -> Result<Vec<u64>> {
+    let (count, nreq) = (in_len.len(), req_stream.len());
+    if keys.len() != 32 * count || ivs.len() != 16 * count || key_status.map_or(false, |k| k.len() != count) ||
+        in_off.len() != count || padding.len() != count || chunk_len.len() != count || start.len() != nreq ||
+        len.len() != nreq || content_off.len() != nreq || hashes.len() < count * HASH_LEN ||
+        status.len() < nreq * 4 || used.len() < nreq * 4 || vouch.len() < nreq * 4 ||
+        !ranges_fit(in_off, in_len, 0, input.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (_, want, _, _) = plain_read_layout(chunk_len, padding, req_stream, start, len, 16)?;
+    if !ranges_fit(content_off, &want, 0, content.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_cread()?;
+    let mut clen = vec![0u64; nreq];
+    check(unsafe {
+        ffi_cread::chipc_read_ranges_dev(keys.as_ptr(), ivs.as_ptr(), key_status.map_or(std::ptr::null(), |k| k.as_ptr()),
+                                         input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), hashes.as_ptr(),
+                                         padding.as_ptr(), chunk_len.as_ptr(), count as u64, req_stream.as_ptr(),
+                                         start.as_ptr(), len.as_ptr(), nreq as u64, content.as_mut_ptr(),
+                                         content_off.as_ptr(), clen.as_mut_ptr(), status.as_mut_ptr() as *mut u32,
+                                         used.as_mut_ptr() as *mut u32, vouch.as_mut_ptr() as *mut u32, flags,
+                                         scratch.ptr, scratch.len() as u64, stream.0)
+    })?;
+    Ok(clen)
 }
 
 #[cfg(test)]

@@ -309,6 +309,29 @@ SNAP_SIGNATURES = {
                                                ctypes.c_void_p, ctypes.c_void_p]),
 }
 
+# the cread header (include/carbonado_hip_cread.h): plaintext ranged reads of
+# level-13 streams (the keystream over ranges, the keys of resident streams, the
+# read), a ninth table of its own
+CREAD_SIGNATURES = {
+    "chipc_abi_version": (ctypes.c_int, []),
+    "chipc_ctr_scratch_len": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "chipc_ctr_ranges_dev": (ctypes.c_int, [c_u8p, c_u8p, ctypes.c_uint64, c_u32p, c_u64p, c_u64p, ctypes.c_uint64,
+                                            ctypes.c_void_p, c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                            ctypes.c_void_p]),
+    "chipc_stream_keys_scratch_len": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "chipc_stream_keys_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, c_u64p, c_u64p,
+                                             ctypes.c_void_p, c_u32p, c_u32p, ctypes.c_uint64, c_u8p, c_u8p, c_u32p,
+                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "chipc_read_layout": (ctypes.c_int, [c_u32p, c_u32p, ctypes.c_uint64, c_u32p, c_u64p, c_u64p, ctypes.c_uint64,
+                                         ctypes.c_uint64, c_u64p, c_u64p, c_u64p, c_u64p]),
+    "chipc_read_scratch_len": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]),
+    "chipc_read_ranges_dev": (ctypes.c_int, [c_u8p, c_u8p, c_u32p, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p,
+                                             c_u32p, c_u32p, ctypes.c_uint64, c_u32p, c_u64p, c_u64p, ctypes.c_uint64,
+                                             ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -331,7 +354,7 @@ def lib() -> ctypes.CDLL:
         l = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES,
                                   **READ_SIGNATURES, **VREAD_SIGNATURES, **ECIES_SIGNATURES,
-                                  **SNAP_SIGNATURES}.items():
+                                  **SNAP_SIGNATURES, **CREAD_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

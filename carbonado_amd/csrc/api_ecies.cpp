@@ -6,6 +6,7 @@
 #include "api_common.hpp"
 #include "ecies_kernels.hpp"
 #include "ecies_plan.hpp"
+#include "key_upload.hpp"
 #include "ragged_plan.hpp"
 
 #include <openssl/rand.h>
@@ -14,57 +15,6 @@ using namespace chip;
 using namespace chip::api;
 
 namespace {
-
-// The pinned copy of a call's table (it holds the keys).  One per thread: the
-// next call waits for the previous upload and wipe before it refills it.
-struct KeyStage {
-    DevBuf pin;
-    hipEvent_t ev = nullptr;
-    bool armed = false;
-};
-thread_local KeyStage t_stage;
-
-// what the host function behind an upload wipes (its own allocation, so that
-// it outlives the thread that made the call)
-struct Wipe {
-    void *p;
-    size_t n;
-};
-
-void wipe_cb(void *u) {
-    auto *w = static_cast<Wipe *>(u);
-    host::secure_wipe(w->p, w->n);
-    delete w;
-}
-
-hipError_t upload_table(std::vector<uint8_t> &table, void *dst, hipStream_t s) {
-    KeyStage &k = t_stage;
-    hipError_t e = hipSuccess;
-    if (k.armed) {
-        e = hipEventSynchronize(k.ev);
-        k.armed = false;
-    }
-    if (e == hipSuccess && !k.ev) e = hipEventCreateWithFlags(&k.ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = grow_pinned(k.pin, table.size());
-    if (e != hipSuccess) {
-        host::secure_wipe(table.data(), table.size());
-        return e;
-    }
-    const size_t n = table.size();
-    std::memcpy(k.pin.p, table.data(), n);
-    host::secure_wipe(table.data(), n);
-    e = hipMemcpyAsync(dst, k.pin.p, n, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-        host::secure_wipe(k.pin.p, n);
-        return e;
-    }
-    Wipe *w = new Wipe{k.pin.p, n};
-    e = hipLaunchHostFunc(s, wipe_cb, w);
-    if (e != hipSuccess) delete w;  // (the next call overwrites the pinned copy; nothing wipes it before)
-    if (e == hipSuccess) e = hipEventRecord(k.ev, s);
-    k.armed = true;
-    return e;
-}
 
 GcmLaunch launch_of(const ecies::Plan &p, uint8_t *scr, const uint8_t *d_in, uint8_t *d_out, uint8_t *d_tag,
                     uint32_t *d_status) {
@@ -93,7 +43,7 @@ int gcm_run(bool seal, ecies::Plan &p, const uint8_t *d_in, uint8_t *d_out, uint
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t *scr = static_cast<uint8_t *>(d_scratch);
-    CHIP_HIP(upload_table(p.table, scr, s));
+    CHIP_HIP(upload_key_table(p.table, scr, s));
     GcmLaunch L = launch_of(p, scr, d_in, d_out, d_tag, d_status);
     L.keep_status = keep_status;
     hipError_t e = gcm_setup_launch(L, s);

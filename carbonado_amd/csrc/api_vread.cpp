@@ -5,34 +5,19 @@
 // caller's scratch and enqueues KA's two checks of the primary slices
 // (audit_kernels.hip, one launch each so that parents and chunks flag
 // different words), the kernels of vread_kernels.hip and KD's read kernel.
-#include "api_common.hpp"
+#include "api_vread.hpp"
 #include "audit_kernels.hpp"
 #include "vread_kernels.hpp"
 
 using namespace chip;
 using namespace chip::api;
 
-extern "C" {
+namespace chip {
+namespace api {
 
-int chipv_abi_version(void) { return CHIPV_ABI_VERSION; }
-
-uint64_t chipv_read_scratch_len(uint64_t nreq, uint64_t nseg) { return vread::scratch_len(nreq, nseg); }
-
-int chipv_read_ranges_dev(const uint8_t *d_streams, const uint64_t *in_off, const uint64_t *in_len,
-                          const uint8_t *d_hash, const uint32_t *padding, const uint32_t *chunk_len, uint64_t nstreams,
-                          const uint32_t *req_stream, const uint64_t *start, const uint64_t *len, uint64_t nreq,
-                          uint8_t *d_content, const uint64_t *content_off, uint64_t *content_len, uint32_t *d_status,
-                          uint32_t *d_used, uint32_t *d_vouch, uint32_t flags, void *d_scratch, uint64_t scratch_len,
-                          void *stream) {
-    if (nreq == 0) return CHIP_OK;
-    vread::Plan vp;
-    int st = vread::plan_vread(reinterpret_cast<uintptr_t>(d_streams), in_off, in_len,
-                               reinterpret_cast<uintptr_t>(d_hash), padding, chunk_len, nstreams, req_stream, start, len,
-                               nreq, reinterpret_cast<uintptr_t>(d_content), content_off, content_len,
-                               d_status && d_used && d_vouch, flags, reinterpret_cast<uintptr_t>(d_scratch), scratch_len,
-                               &vp);
-    if (st != CHIP_OK) return st;
-    st = use_device();
+int vread_enqueue(vread::Plan &vp, uint32_t *d_status, uint32_t *d_used, uint32_t *d_vouch, uint32_t flags,
+                  void *d_scratch, void *stream) {
+    int st = use_device();
     if (st != CHIP_OK) return st;
     Ctx *c;
     st = ctx_get(&c);
@@ -79,6 +64,32 @@ int chipv_read_ranges_dev(const uint8_t *d_streams, const uint64_t *in_off, cons
     CHIP_HIP(vread_finish_launch(V, s));
     CHIP_HIP(read_copy_launch(L, s));
     return CHIP_OK;
+}
+
+}  // namespace api
+}  // namespace chip
+
+extern "C" {
+
+int chipv_abi_version(void) { return CHIPV_ABI_VERSION; }
+
+uint64_t chipv_read_scratch_len(uint64_t nreq, uint64_t nseg) { return vread::scratch_len(nreq, nseg); }
+
+int chipv_read_ranges_dev(const uint8_t *d_streams, const uint64_t *in_off, const uint64_t *in_len,
+                          const uint8_t *d_hash, const uint32_t *padding, const uint32_t *chunk_len, uint64_t nstreams,
+                          const uint32_t *req_stream, const uint64_t *start, const uint64_t *len, uint64_t nreq,
+                          uint8_t *d_content, const uint64_t *content_off, uint64_t *content_len, uint32_t *d_status,
+                          uint32_t *d_used, uint32_t *d_vouch, uint32_t flags, void *d_scratch, uint64_t scratch_len,
+                          void *stream) {
+    if (nreq == 0) return CHIP_OK;
+    vread::Plan vp;
+    int st = vread::plan_vread(reinterpret_cast<uintptr_t>(d_streams), in_off, in_len,
+                               reinterpret_cast<uintptr_t>(d_hash), padding, chunk_len, nstreams, req_stream, start, len,
+                               nreq, reinterpret_cast<uintptr_t>(d_content), content_off, content_len,
+                               d_status && d_used && d_vouch, flags, reinterpret_cast<uintptr_t>(d_scratch), scratch_len,
+                               &vp);
+    if (st != CHIP_OK) return st;
+    return vread_enqueue(vp, d_status, d_used, d_vouch, flags, d_scratch, stream);
 }
 
 }  // extern "C"

@@ -838,6 +838,141 @@ def decode_ragged_ecies(fmt: int, secret_key: bytes, enc: torch.Tensor, in_off, 
     return olen[:count].tolist()
 
 
+# ---- plaintext ranged reads of level-13 streams (include/carbonado_hip_cread.h):
+# the keystream over ranges, the keys of resident streams, the read
+
+def ctr_scratch(nkeys: int, nitems: int, device=None) -> torch.Tensor:
+    """Scratch of a ctr_ranges call over nitems items under nkeys keys."""
+    size = _lib.lib().chipc_ctr_scratch_len(nkeys, nitems)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def ctr_ranges(keys, ivs, item_key, pos, n, buf: torch.Tensor, buf_off, scratch: torch.Tensor,
+               gate: torch.Tensor | None = None) -> None:
+    """Item i XORs buf[buf_off[i] : buf_off[i] + n[i]] (16-B aligned) in place
+    with keystream bytes [pos[i], pos[i] + n[i]) of AES-256-GCM (16-byte nonce)
+    under keys[32 k : 32 k + 32] and ivs[16 k : 16 k + 16], k = item_key[i]
+    (host bytes).  The same call encrypts and decrypts.  gate: None, or int32 /
+    uint32 [nitems] on the device: item i is skipped where gate[i] != 0.  The
+    key region of the scratch is zeroed by the call's last operation.  Enqueued
+    on the current stream, not synchronised."""
+    assert buf.is_cuda and scratch.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous()
+    ik, pik, nitems = _arr(item_key, np.uint32)
+    ps, pps, npos = _arr(pos)
+    ln, pln, nl = _arr(n)
+    off, poff, no = _arr(buf_off)
+    assert npos == nitems == nl == no and _fits(off, ln[:nitems], buf.numel())
+    nkeys = len(bytes(keys)) // 32 if not isinstance(keys, np.ndarray) else keys.size // 32
+    kk, pk, vv, pv = _gcm_keys(keys, ivs, nkeys)
+    if gate is not None:
+        assert gate.is_cuda and gate.numel() >= nitems and gate.element_size() == 4 and gate.is_contiguous()
+    check(_lib.lib().chipc_ctr_ranges_dev(pk, pv, nkeys, pik, pps, pln, nitems, _p(buf), poff,
+                                          _p(gate) if gate is not None else None, _p(scratch), scratch.numel(),
+                                          _stream()))
+
+
+def stream_keys_scratch(nstreams: int, device=None) -> torch.Tensor:
+    """Scratch of a stream_keys call over nstreams streams."""
+    size = _lib.lib().chipc_stream_keys_scratch_len(nstreams)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def stream_keys(secret_key: bytes, streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len,
+                scratch: torch.Tensor):
+    """The AES key and nonce of every level-13 stream, from envelope bytes
+    [0, 81) read by a strict vouched read (so only from bytes hashed against
+    the root) and one key agreement per stream on the host.  The call waits
+    once, for the header bytes.  Returns (keys uint8 [nstreams, 32], ivs uint8
+    [nstreams, 16], key_status uint32 [nstreams]) as numpy arrays: status 0, 5
+    or 7 for a header that cannot be served, ECIES_FAILED for an object shorter
+    than 97 bytes or an ephemeral key that does not parse (key and nonce are
+    zeros then).  The keys are the caller's to hold and wipe."""
+    assert streams.is_cuda and hashes.is_cuda and scratch.is_cuda and streams.dtype == torch.uint8
+    assert streams.is_contiguous() and hashes.is_contiguous()
+    ioff, pioff, nstreams = _arr(in_off)
+    ilen, pilen, nl = _arr(in_len)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    cl, pcl, ncl = _arr(chunk_len, np.uint32)
+    assert nl == nstreams == npad == ncl
+    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
+    keys = np.zeros((max(nstreams, 1), 32), dtype=np.uint8)
+    ivs = np.zeros((max(nstreams, 1), 16), dtype=np.uint8)
+    status = np.zeros(max(nstreams, 1), dtype=np.uint32)
+    check(_lib.lib().chipc_stream_keys_dev(bytes(secret_key), len(secret_key), _p(streams), pioff, pilen, _p(hashes),
+                                           ppad, pcl, nstreams, keys.ctypes.data_as(_lib.c_u8p),
+                                           ivs.ctypes.data_as(_lib.c_u8p), status.ctypes.data_as(_lib.c_u32p),
+                                           _p(scratch), scratch.numel(), _stream()))
+    return keys[:nstreams], ivs[:nstreams], status[:nstreams]
+
+
+def plain_read_layout(chunk_len, padding, req_stream, start, length, align: int = 16):
+    """read_layout for requests in plaintext bytes of level-13 streams: (content_off,
+    content_len, content_total, nseg) of plaintext [start, min(P, start +
+    length)), P = 4 chunk_len - padding - 97."""
+    cl, pcl, nstreams = _arr(chunk_len, np.uint32)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    rs, prs, nreq = _arr(req_stream, np.uint32)
+    st, pst, ns = _arr(start)
+    ln, pln, nl = _arr(length)
+    assert npad == nstreams and ns == nreq == nl
+    off, clen = np.zeros(max(nreq, 1), dtype=np.uint64), np.zeros(max(nreq, 1), dtype=np.uint64)
+    total, nseg = ctypes.c_uint64(), ctypes.c_uint64()
+    check(_lib.lib().chipc_read_layout(pcl, ppad, nstreams, prs, pst, pln, nreq, align, off.ctypes.data_as(_lib.c_u64p),
+                                       clen.ctypes.data_as(_lib.c_u64p), ctypes.byref(total), ctypes.byref(nseg)))
+    return off[:nreq].tolist(), clen[:nreq].tolist(), total.value, nseg.value
+
+
+def plain_read_scratch(nreq: int, nseg: int, nstreams: int, device=None) -> torch.Tensor:
+    """Scratch of a read_plain_ranges call of nreq requests in nseg segments (plain_read_layout)."""
+    size = _lib.lib().chipc_read_scratch_len(nreq, nseg, nstreams)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def read_plain_ranges(keys, ivs, key_status, streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding,
+                      chunk_len, req_stream, start, length, content: torch.Tensor, content_off, status: torch.Tensor,
+                      used: torch.Tensor, vouch: torch.Tensor, scratch: torch.Tensor, flags: int = 0):
+    """Plaintext bytes [start[r], start[r] + length[r]) of level-13 stream
+    req_stream[r] into content[content_off[r] :] (plain_read_layout), with keys,
+    ivs and key_status as stream_keys gave them (key_status may be None): the
+    vouched read of the envelope bytes behind the range, then the keystream
+    taken off in place, gated on the read's status.  status, used and vouch as
+    read_ranges_vouched fills them; a request whose stream has a non-zero
+    key_status gets that status, zeros, used 0 and vouch 0.  The GCM tag is NOT
+    checked: the ciphertext is vouched for by the root hash, and a wrong key
+    gives status 0 and bytes that are not the plaintext.  Enqueued on the
+    current stream, not synchronised.  Returns the content length per request."""
+    assert streams.is_cuda and content.is_cuda and hashes.is_cuda and status.is_cuda and used.is_cuda and scratch.is_cuda
+    assert vouch.is_cuda
+    assert streams.dtype == content.dtype == torch.uint8 and streams.dim() == content.dim() == 1
+    assert streams.is_contiguous() and content.is_contiguous() and hashes.is_contiguous()
+    ioff, pioff, nstreams = _arr(in_off)
+    ilen, pilen, nl = _arr(in_len)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    cl, pcl, ncl = _arr(chunk_len, np.uint32)
+    rs, prs, nreq = _arr(req_stream, np.uint32)
+    st, pst, ns = _arr(start)
+    ln, pln, nln = _arr(length)
+    coff, pcoff, nco = _arr(content_off)
+    assert nl == nstreams == npad == ncl and ns == nreq == nln == nco
+    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
+    for t in (status, used, vouch):
+        assert t.numel() >= nreq and t.element_size() == 4 and t.is_contiguous()
+    if nreq and int(rs.max()) < nstreams:  # the content buffer is checked before the call (else: the call reports it)
+        _, want, _, _ = plain_read_layout(cl[:nstreams], pad[:nstreams], rs[:nreq], st[:nreq], ln[:nreq])
+        assert _fits(coff, np.asarray(want, dtype=np.uint64), content.numel())
+    kk, pk, vv, pv = _gcm_keys(keys, ivs, nstreams)
+    pks = None
+    if key_status is not None:
+        ks, pks, nks = _arr(key_status, np.uint32)
+        assert nks == nstreams
+    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
+    check(_lib.lib().chipc_read_ranges_dev(pk, pv, pks, _p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams, prs,
+                                           pst, pln, nreq, _p(content), pcoff, clen.ctypes.data_as(_lib.c_u64p),
+                                           _p(status), _p(used), _p(vouch), flags, _p(scratch), scratch.numel(),
+                                           _stream()))
+    return clen[:nreq].tolist()
+
+
 # ---- snappy on the device (include/carbonado_hip_snap.h): the framing format
 # of encoding::snap / decoding::snap over ragged batches, bit-exact with
 # chip_snap_compress, and the one-call forms of formats 6, 7, 10, 11, 14, 15
