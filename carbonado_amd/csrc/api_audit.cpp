@@ -19,15 +19,7 @@ int enqueue(audit::Plan &p, bool verify, bool proofs, uint32_t *d_status, void *
     if (st != CHIP_OK) return st;
     uint8_t *scr = static_cast<uint8_t *>(d_scratch);
     CHIP_HIP(h2d(c->stage, scr, p.table.data(), p.table.size(), s));
-    AuditLaunch L{};
-    L.reqs = reinterpret_cast<const audit::Req *>(scr + p.lay.reqs);
-    L.parents = reinterpret_cast<const uint64_t *>(scr + p.lay.parents);
-    L.chunks = reinterpret_cast<const uint64_t *>(scr + p.lay.chunks);
-    L.units = reinterpret_cast<const uint64_t *>(scr + p.lay.units);
-    L.nreq = p.nreq;
-    L.total_parents = p.total_parents;
-    L.total_chunks = p.total_chunks;
-    L.total_units = p.total_units;
+    AuditLaunch L = audit_launch_of(p, scr);
     L.proofs = proofs;
     L.status = d_status;
     if (verify) {

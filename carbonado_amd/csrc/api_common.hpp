@@ -38,6 +38,7 @@
 #include "chip_internal.hpp"
 #include "gf256.hpp"
 #include "host_stages.hpp"
+#include "stream_rules.hpp"
 
 #define CHIP_HIP(expr)                                  \
     do {                                                \

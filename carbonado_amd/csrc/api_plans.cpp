@@ -10,10 +10,9 @@ namespace api {
 bool valid_km(uint32_t k, uint32_t m) { return k >= 1 && m >= k && m <= 256; }
 
 void calc_pad(uint64_t n, uint32_t k, uint32_t *pad, uint64_t *C) {
-    const uint64_t unit = 1024ull * k;
-    const uint64_t target = (n + unit - 1) / unit * unit;
-    *pad = (uint32_t)(target - n);
-    *C = target / k;
+    const rules::Pad p = rules::calc_pad(n, k);
+    *pad = p.pad;
+    *C = p.C;
 }
 
 // encode plan: rows 0..k-1 copied, k..m-1 computed from the enc_matrix
@@ -221,7 +220,7 @@ int select_shares(uint32_t k, uint32_t m, const uint32_t *idx, uint32_t nshares,
     return sel_pos->size() == k ? CHIP_OK : CHIP_ERR_ZFEC;
 }
 
-uint64_t n_chunks_of(uint64_t n) { return n == 0 ? 1 : (n + 1023) / 1024; }
+uint64_t n_chunks_of(uint64_t n) { return rules::chunks(n); }
 
 int ceil_log2_u64(uint64_t x) { return x <= 1 ? 0 : 64 - __builtin_clzll(x - 1); }
 
@@ -383,19 +382,7 @@ int zfec_decode_device(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t in_
     return CHIP_OK;
 }
 
-// The content length n of a bao stream of `len` bytes (bao_encoded_len is
-// strictly increasing): false when no n gives exactly `len`.
-bool bao_content_len(uint64_t len, uint64_t *n) {
-    if (len < 8) return false;
-    uint64_t lo = 0, hi = len - 8;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (bao_encoded_len(mid) < len) lo = mid + 1;
-        else hi = mid;
-    }
-    *n = lo;
-    return bao_encoded_len(lo) == len;
-}
+bool bao_content_len(uint64_t len, uint64_t *n) { return rules::bao_content(len, n); }
 
 // bao-encode `n` device bytes into c->out; hash to host
 int bao_encode_ctx(Ctx *c, const uint8_t *d_in, uint64_t n, bool want_stream,
@@ -491,18 +478,12 @@ bool slice_ok(uint64_t n, uint64_t c0, uint64_t c1, const std::vector<uint8_t> &
 int scrub_repair_enqueue(Ctx *c, const uint8_t *d_stream, uint64_t n, uint64_t len,
                                 const std::vector<uint32_t> &good, uint32_t padding, uint64_t C, uint8_t *d_dst,
                                 uint8_t *d_h2) {
-    if (good.size() < CHIP_FEC_K) return CHIP_ERR_ZFEC;
-    const uint64_t kc = (uint64_t)CHIP_FEC_K * C;
-    if (padding > kc) return CHIP_ERR_ZFEC;
-    const uint64_t dl = kc - padding;
-    uint32_t pad2;
-    uint64_t C2;
-    calc_pad(dl, CHIP_FEC_K, &pad2, &C2);
-    if (pad2 != padding) return CHIP_ERR_SCRUBBED_PADDING_MISMATCH;  // decoding.rs:192-194
-    const uint64_t z2 = (uint64_t)CHIP_FEC_M * C2;
-    if (bao_encoded_len(z2) != len) return CHIP_ERR_SCRUBBED_LENGTH_MISMATCH;  // decoding.rs:198-203
+    int st = rules::scrub_verdict(len, C, padding, (uint32_t)good.size());
+    if (st != rules::REPAIR) return st;
+    const uint64_t kc = (uint64_t)CHIP_FEC_K * C, dl = kc - padding;  // the decoded object and its own shard length
+    const uint64_t C2 = rules::calc_pad(dl, CHIP_FEC_K).C, z2 = (uint64_t)CHIP_FEC_M * C2;
     std::vector<uint32_t> pos;
-    int st = select_shares(CHIP_FEC_K, CHIP_FEC_M, good.data(), (uint32_t)good.size(), &pos);
+    st = select_shares(CHIP_FEC_K, CHIP_FEC_M, good.data(), (uint32_t)good.size(), &pos);
     if (st != CHIP_OK) return st;
     // content of all shards, parents stripped
     CHIP_HIP(grow(c->mid, n));

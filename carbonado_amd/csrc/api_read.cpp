@@ -43,31 +43,16 @@ int chipd_read_ranges_dev(const uint8_t *d_streams, const uint64_t *in_off, cons
     if (st != CHIP_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t *scr = static_cast<uint8_t *>(d_scratch);
-    const audit::ScratchLayout &ka = p.ka.lay;
     CHIP_HIP(h2d(c->stage, scr, p.ka.table.data(), p.ka.table.size(), s));
-    ReadLaunch L{};
-    L.slices = reinterpret_cast<const audit::Req *>(scr + p.lay.audit + ka.reqs);
-    L.parents = reinterpret_cast<const uint64_t *>(scr + p.lay.audit + ka.parents);
-    L.chunks = reinterpret_cast<const uint64_t *>(scr + p.lay.audit + ka.chunks);
-    L.masks = reinterpret_cast<const read::MaskEntry *>(scr + p.lay.masks);
-    L.reqs = reinterpret_cast<const read::Req *>(scr + p.lay.reqs);
-    L.segs = reinterpret_cast<const read::Seg *>(scr + p.lay.segs);
-    L.fpar = reinterpret_cast<const uint64_t *>(scr + p.lay.fpar);
-    L.blocks = reinterpret_cast<const uint64_t *>(scr + p.lay.blocks);
-    L.rstat = reinterpret_cast<uint32_t *>(scr + p.lay.rstat);
-    L.served = reinterpret_cast<read::Served *>(scr + p.lay.served);
-    L.nreq = p.nreq; L.nseg = p.nseg; L.total_blocks = p.total_blocks;
-    L.prim_parents = p.prim_parents; L.prim_chunks = p.prim_chunks; L.fb_parents = p.fb_parents;
-    L.status = d_status; L.used = d_used;
+    const ReadLaunch L = read_launch_of(p, scr, d_status, d_used);
     if (p.nseg) {
         CHIP_HIP(hipMemsetAsync(L.rstat, 0, read::M * p.nseg * sizeof(uint32_t), s));
-        AuditLaunch A{};  // KA's checks of every segment's own slice
-        A.reqs = L.slices; A.parents = L.parents; A.chunks = L.chunks; A.units = nullptr;
-        A.nreq = p.nseg; A.total_parents = p.prim_parents; A.total_chunks = p.prim_chunks; A.total_units = 0;
+        AuditLaunch A = audit_launch_of(p.ka, scr + p.lay.audit);  // KA's checks of every segment's own slice
+        A.total_units = 0;
         A.proofs = false;
         A.status = L.rstat;
         CHIP_HIP(audit_verify_launch(A, s));
-        CHIP_HIP(read_fallback_launch(L, s));
+        CHIP_HIP(read_fallback_launch(L, nullptr, s));
     }
     CHIP_HIP(read_serve_launch(L, s));
     return CHIP_OK;

@@ -4,8 +4,8 @@
 // table are host code in repair_plan.hpp; this file uploads the tables into
 // the caller's scratch and enqueues KA's checks (audit_kernels.hip), the
 // kernels of repair_kernels.hip and KR's encode (ragged_kernels.hip) behind
-// them.  chip_scrub_batch_dev (api_scrub.cpp) is the uniform call and shares
-// nothing with this one but select_shares.
+// them.  chip_scrub_batch_dev (api_scrub.cpp) is the uniform call; the two
+// share select_shares and the verdicts behind the mask (stream_rules.hpp).
 #include "api_common.hpp"
 #include "audit_kernels.hpp"
 #include "ragged_kernels.hpp"
@@ -32,14 +32,7 @@ int verdicts_enqueue(Ctx *c, uintptr_t d_in, const uint64_t *in_off, const std::
     if (p.nreq) {
         CHIP_HIP(h2d(c->stage, scr + V.audit, p.table.data(), p.table.size(), s));
         CHIP_HIP(hipMemsetAsync(rstat, 0, p.nreq * sizeof(uint32_t), s));
-        AuditLaunch L{};
-        L.reqs = reinterpret_cast<const audit::Req *>(scr + V.audit + p.lay.reqs);
-        L.parents = reinterpret_cast<const uint64_t *>(scr + V.audit + p.lay.parents);
-        L.chunks = reinterpret_cast<const uint64_t *>(scr + V.audit + p.lay.chunks);
-        L.units = reinterpret_cast<const uint64_t *>(scr + V.audit + p.lay.units);
-        L.nreq = p.nreq;
-        L.total_parents = p.total_parents;
-        L.total_chunks = p.total_chunks;
+        AuditLaunch L = audit_launch_of(p, scr + V.audit);
         L.total_units = 0;  // verdicts only: no content is gathered
         L.proofs = false;
         L.status = rstat;

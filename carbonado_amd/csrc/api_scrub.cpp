@@ -223,17 +223,12 @@ int chip_scrub_batch_dev(const uint8_t *d_in, uint64_t in_stride, uint64_t len, 
     const uint64_t kc = (uint64_t)CHIP_FEC_K * C;
     struct Rep { uint64_t o; std::vector<uint32_t> sel; };
     std::vector<Rep> reps;
-    uint32_t pad2 = 0;
-    uint64_t C2 = 0;
-    const bool pad_ok = padding <= kc;
-    if (pad_ok) calc_pad(kc - padding, CHIP_FEC_K, &pad2, &C2);
-    for (uint64_t o : repair) {  // the host-side verdicts, as scrub_repair_enqueue's order
+    for (uint64_t o : repair) {
         std::vector<uint32_t> good, pos;
         for (uint32_t i = 0; i < CHIP_FEC_M; ++i)
             if (m[o] >> i & 1) good.push_back(i);
-        if (!pad_ok) { status[o] = CHIP_ERR_ZFEC; continue; }
-        if (pad2 != padding) { status[o] = CHIP_ERR_SCRUBBED_PADDING_MISMATCH; continue; }
-        if (bao_encoded_len((uint64_t)CHIP_FEC_M * C2) != len) { status[o] = CHIP_ERR_SCRUBBED_LENGTH_MISMATCH; continue; }
+        const int verdict = rules::scrub_verdict(len, C, padding, (uint32_t)good.size());
+        if (verdict != rules::REPAIR) { status[o] = verdict; continue; }
         if (select_shares(CHIP_FEC_K, CHIP_FEC_M, good.data(), (uint32_t)good.size(), &pos) != CHIP_OK) {
             status[o] = CHIP_ERR_ZFEC;
             continue;
@@ -243,6 +238,8 @@ int chip_scrub_batch_dev(const uint8_t *d_in, uint64_t in_stride, uint64_t len, 
         reps.push_back(std::move(r));
     }
     std::stable_sort(reps.begin(), reps.end(), [](const Rep &a, const Rep &b) { return a.sel < b.sel; });
+    // the decoded objects' own shard length (a repair passed the verdicts: padding <= kc)
+    const uint64_t C2 = reps.empty() ? 0 : rules::calc_pad(kc - padding, CHIP_FEC_K).C;
     const uint64_t z2 = (uint64_t)CHIP_FEC_M * C2, lstride = (len + 15) & ~uint64_t(15);
     for (size_t g0 = 0; g0 < reps.size(); g0 += kScrubGroup) {
         const size_t R = std::min(kScrubGroup, reps.size() - g0);

@@ -25,40 +25,26 @@ int vread_enqueue(vread::Plan &vp, uint32_t *d_status, uint32_t *d_used, uint32_
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t *scr = static_cast<uint8_t *>(d_scratch);
     read::Plan &p = vp.rd;
-    const audit::ScratchLayout &ka = p.ka.lay;
     CHIP_HIP(h2d(c->stage, scr, p.ka.table.data(), p.ka.table.size(), s));
     VreadLaunch V{};
-    ReadLaunch &L = V.rd;
-    L.slices = reinterpret_cast<const audit::Req *>(scr + p.lay.audit + ka.reqs);
-    L.parents = reinterpret_cast<const uint64_t *>(scr + p.lay.audit + ka.parents);
-    L.chunks = reinterpret_cast<const uint64_t *>(scr + p.lay.audit + ka.chunks);
-    L.masks = reinterpret_cast<const read::MaskEntry *>(scr + p.lay.masks);
-    L.reqs = reinterpret_cast<const read::Req *>(scr + p.lay.reqs);
-    L.segs = reinterpret_cast<const read::Seg *>(scr + p.lay.segs);
-    L.fpar = reinterpret_cast<const uint64_t *>(scr + p.lay.fpar);
-    L.blocks = reinterpret_cast<const uint64_t *>(scr + p.lay.blocks);
-    L.rstat = reinterpret_cast<uint32_t *>(scr + p.lay.rstat);
-    L.served = reinterpret_cast<read::Served *>(scr + p.lay.served);
-    L.nreq = p.nreq; L.nseg = p.nseg; L.total_blocks = p.total_blocks;
-    L.prim_parents = p.prim_parents; L.prim_chunks = p.prim_chunks; L.fb_parents = p.fb_parents;
-    L.status = d_status; L.used = d_used;
+    V.rd = read_launch_of(p, scr, d_status, d_used);
+    const ReadLaunch &L = V.rd;
     V.pathw = reinterpret_cast<uint32_t *>(scr + vp.lay.path);
     V.contra = reinterpret_cast<uint32_t *>(scr + vp.lay.contra);
     V.vouch = d_vouch;
     V.strict = flags & CHIPV_STRICT;
     if (p.nseg) {
         CHIP_HIP(hipMemsetAsync(scr + vp.lay.zero_from(), 0, vp.lay.zero_len(), s));
-        AuditLaunch A{};  // KA's checks of every segment's own slice: the parents into the path words,
-        A.reqs = L.slices; A.parents = L.parents; A.chunks = L.chunks; A.units = nullptr;
-        A.nreq = p.nseg; A.total_units = 0;
+        AuditLaunch A = audit_launch_of(p.ka, scr + p.lay.audit);  // KA's checks of every segment's own slice:
+        A.total_units = 0;
         A.proofs = false;
-        A.total_parents = p.prim_parents; A.total_chunks = 0;
+        A.total_chunks = 0;  // the parents into the path words,
         A.status = V.pathw;
         CHIP_HIP(audit_verify_launch(A, s));
         A.total_parents = 0; A.total_chunks = p.prim_chunks;  // the chunks (and the header) into the chunk words
         A.status = L.rstat;
         CHIP_HIP(audit_verify_launch(A, s));
-        CHIP_HIP(vread_fallback_launch(V, s));
+        CHIP_HIP(read_fallback_launch(L, V.pathw, s));
         CHIP_HIP(vread_vouch_launch(V, s));
     }
     CHIP_HIP(vread_finish_launch(V, s));

@@ -20,18 +20,6 @@ using namespace bao;
 
 constexpr int TPB = 256, QUADS = TPB / 4;
 
-// the request of work item i: pre[r] <= i < pre[r + 1] (pre[0] = 0, pre[nreq] > i;
-// requests without items are passed over)
-__device__ __forceinline__ uint32_t find_req(const uint64_t *pre, uint32_t nreq, uint64_t i) {
-    uint32_t lo = 0, hi = nreq;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ uint32_t hash_word(const uint8_t *h, int w) {  // any alignment
     return (uint32_t)h[4 * w] | (uint32_t)h[4 * w + 1] << 8 | (uint32_t)h[4 * w + 2] << 16 |
            (uint32_t)h[4 * w + 3] << 24;

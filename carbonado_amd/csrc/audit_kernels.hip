@@ -47,7 +47,7 @@ __global__ __launch_bounds__(TPB) void audit_parent_kernel(const Req *reqs, cons
                                                            uint64_t total, uint32_t *status) {
     const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
     if (i >= total) return;
-    const uint32_t r = find_req(pre, nreq, i);
+    const uint32_t r = prefix_find(pre, nreq, i);
     const Req a = reqs[r];
     if (!parent_ok<PROOF>(a, i - pre[r])) flag_mismatch(status, r);
 }
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(TPB) void audit_chunk_kernel(const Req *reqs, const
     const int t = threadIdx.x;
     const uint64_t i = (uint64_t)blockIdx.x * QUADS + (t >> 2);
     if (i >= total) return;  // whole quads leave; the kernel has no workgroup barrier
-    const uint32_t r = find_req(pre, nreq, i);
+    const uint32_t r = prefix_find(pre, nreq, i);
     const Req a = reqs[r];
     if (!chunk_ok<PROOF>(a, i - pre[r], msg, t)) flag_mismatch(status, r);
 }
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(TPB) void audit_content_kernel(const Req *reqs, con
                                                             uint64_t total, const uint32_t *status) {
     const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
     if (i >= total) return;
-    const uint32_t r = find_req(pre, nreq, i);
+    const uint32_t r = prefix_find(pre, nreq, i);
     const Req a = reqs[r];
     const uint64_t o = UNIT * (i - pre[r]), left = a.olen - o;  // content bytes [o, o + 16) of the request
     uint8_t *dst = reinterpret_cast<uint8_t *>(a.dst) + o;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(TPB) void audit_extract_kernel(const Req *reqs, con
                                                             const uint64_t *parents, uint32_t nreq, uint64_t total) {
     const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
     if (i >= total) return;
-    const uint32_t r = find_req(pre, nreq, i);
+    const uint32_t r = prefix_find(pre, nreq, i);
     const Req a = reqs[r];
     const uint8_t *src = reinterpret_cast<const uint8_t *>(a.src);
     uint8_t *dst = reinterpret_cast<uint8_t *>(a.dst);
@@ -114,15 +114,13 @@ __global__ __launch_bounds__(TPB) void audit_extract_kernel(const Req *reqs, con
     else store16_partial(d, load16_partial(p, (uint32_t)(clen - w)), (uint32_t)(clen - w));
 }
 
-inline unsigned blocks(uint64_t items, uint64_t per) { return (unsigned)((items + per - 1) / per); }
-
 }  // namespace audit
 
 hipError_t audit_extract_launch(const AuditLaunch &L, hipStream_t stream) {
     using namespace audit;
     if (L.total_units)
-        hipLaunchKernelGGL(audit_extract_kernel, dim3(blocks(L.total_units, TPB)), dim3(TPB), 0, stream, L.reqs, L.units,
-                           L.parents, (uint32_t)L.nreq, L.total_units);
+        hipLaunchKernelGGL(audit_extract_kernel, dim3(nblocks(L.total_units, TPB)), dim3(TPB), 0, stream, L.reqs,
+                           L.units, L.parents, (uint32_t)L.nreq, L.total_units);
     return hipGetLastError();
 }
 
@@ -131,17 +129,17 @@ hipError_t audit_verify_launch(const AuditLaunch &L, hipStream_t stream) {
     const uint32_t nreq = (uint32_t)L.nreq;
     if (L.total_parents) {
         const auto k = L.proofs ? audit_parent_kernel<true> : audit_parent_kernel<false>;
-        hipLaunchKernelGGL(k, dim3(blocks(L.total_parents, TPB)), dim3(TPB), 0, stream, L.reqs, L.parents, nreq,
+        hipLaunchKernelGGL(k, dim3(nblocks(L.total_parents, TPB)), dim3(TPB), 0, stream, L.reqs, L.parents, nreq,
                            L.total_parents, L.status);
     }
     if (L.total_chunks) {
         const auto k = L.proofs ? audit_chunk_kernel<true> : audit_chunk_kernel<false>;
-        hipLaunchKernelGGL(k, dim3(blocks(L.total_chunks, QUADS)), dim3(TPB), 0, stream, L.reqs, L.chunks, nreq,
+        hipLaunchKernelGGL(k, dim3(nblocks(L.total_chunks, QUADS)), dim3(TPB), 0, stream, L.reqs, L.chunks, nreq,
                            L.total_chunks, L.status);
     }
     if (L.total_units) {  // behind the verdicts, in stream order
         const auto k = L.proofs ? audit_content_kernel<true> : audit_content_kernel<false>;
-        hipLaunchKernelGGL(k, dim3(blocks(L.total_units, TPB)), dim3(TPB), 0, stream, L.reqs, L.units, nreq,
+        hipLaunchKernelGGL(k, dim3(nblocks(L.total_units, TPB)), dim3(TPB), 0, stream, L.reqs, L.units, nreq,
                            L.total_units, L.status);
     }
     return hipGetLastError();

@@ -18,6 +18,22 @@ struct AuditLaunch {
     uint32_t *status;         // verify: [nreq], zero at launch
 };
 
+// The launch table of a plan whose uploaded table lies at `base` on the
+// device.  The caller sets `proofs` and `status`, and zeroes the totals of the
+// launches it leaves out.
+inline AuditLaunch audit_launch_of(const audit::Plan &p, const uint8_t *base) {
+    AuditLaunch L{};
+    L.reqs = reinterpret_cast<const audit::Req *>(base + p.lay.reqs);
+    L.parents = reinterpret_cast<const uint64_t *>(base + p.lay.parents);
+    L.chunks = reinterpret_cast<const uint64_t *>(base + p.lay.chunks);
+    L.units = reinterpret_cast<const uint64_t *>(base + p.lay.units);
+    L.nreq = p.nreq;
+    L.total_parents = p.total_parents;
+    L.total_chunks = p.total_chunks;
+    L.total_units = p.total_units;
+    return L;
+}
+
 // Enqueue the gather of every request's proof (one launch).
 hipError_t audit_extract_launch(const AuditLaunch &L, hipStream_t stream);
 

@@ -37,6 +37,21 @@ AUDIT_HD int clog2(uint64_t x) { return x <= 1 ? 0 : 64 - __builtin_clzll(x - 1)
 
 AUDIT_HD uint64_t umin(uint64_t a, uint64_t b) { return a < b ? a : b; }
 
+// The owner of work item i in a prefix array: pre[r] <= i < pre[r + 1]
+// (pre[0] = 0, pre[count] > i; owners without items are passed over).  Every
+// kernel that finds its request, segment or repair by its index goes through
+// this, and so does the host where it enumerates the same items.
+template <typename T>
+AUDIT_HD uint32_t prefix_find(const T *pre, uint32_t count, T i) {
+    uint32_t lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (pre[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // c(s)
 AUDIT_HD int parents_at(uint64_t s, uint64_t N) {
     const int cl = clog2(N - s);

@@ -9,14 +9,20 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <utility>
 #include <vector>
 
 #include "../../include/carbonado_hip_audit.h"
 #include "audit_nodes.hpp"
+#include "stream_rules.hpp"
 
 namespace chip {
 namespace audit {
+
+using rules::bao_content;
+using rules::bao_len;
+using rules::chunks;
+using rules::ranges_overlap;
+using rules::up;
 
 constexpr uint64_t MAX_SLICE = 1ull << 53;  // index and count: start + len stays u64
 constexpr uint64_t MAX_ITEMS = 1ull << 36;  // work items of one kind per call (a grid of < 2^31 workgroups)
@@ -35,23 +41,6 @@ struct Req {
     uint64_t olen;   // content bytes handed out
 };
 static_assert(sizeof(Req) == 64, "record layout");
-
-inline uint64_t chunks(uint64_t n) { return n == 0 ? 1 : (n + 1023) / 1024; }
-inline uint64_t bao_len(uint64_t n) { return 8 + n + 64 * (chunks(n) - 1); }
-inline uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-
-// content length of a bao stream of `len` bytes (false: no such stream)
-inline bool bao_content(uint64_t len, uint64_t *n) {
-    if (len < 8) return false;
-    uint64_t lo = 0, hi = len - 8;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (bao_len(mid) < len) lo = mid + 1;
-        else hi = mid;
-    }
-    *n = lo;
-    return bao_len(lo) == len;
-}
 
 // What a request (index, count <= MAX_SLICE) selects of n content bytes, in
 // chunk units: start and len are multiples of 1024, so nothing can wrap.
@@ -118,26 +107,6 @@ struct Plan {
 
 // 16-B work items of a request's proof gather: the header, 4 per parent, 64 per chunk
 inline uint64_t extract_units(uint64_t parents, uint64_t nchunks) { return 1 + 4 * parents + 64 * nchunks; }
-
-// true when two of the ranges [off[r], off[r] + len[r]) with len[r] > 0 share a byte
-inline bool ranges_overlap(const uint64_t *off, const uint64_t *len, uint64_t count) {
-    // ranges in ascending order (what layout() hands out) need one pass and no sort
-    uint64_t end = 0, o = 0;
-    for (; o < count; ++o) {
-        if (!len[o]) continue;
-        if (off[o] < end) break;
-        end = off[o] + len[o];
-    }
-    if (o == count) return false;
-    std::vector<std::pair<uint64_t, uint64_t>> r;
-    r.reserve(count);
-    for (o = 0; o < count; ++o)
-        if (len[o]) r.emplace_back(off[o], len[o]);
-    std::sort(r.begin(), r.end());
-    for (size_t i = 1; i < r.size(); ++i)
-        if (r[i - 1].first + r[i - 1].second > r[i].first) return true;
-    return false;
-}
 
 // One request into the table; the prefix entries hold this request's counts
 // until finish() turns them into prefix sums.

@@ -27,6 +27,9 @@ constexpr uint64_t NO_OUT = ~0ull;
 constexpr int ZF_MAXK = 16;  // fast kernel: up to 16 input shards
 constexpr int ZF_MAXP = 8;   // fast kernel: up to 8 computed rows (2 dword groups)
 
+// workgroups of a launch over `items` work items, `per` of them a workgroup
+inline unsigned nblocks(uint64_t items, uint64_t per) { return (unsigned)((items + per - 1) / per); }
+
 // One GF(2^8) "matrix apply" over stripes of `count` objects:
 //   out_row[p] = XOR_j coef[p][j] * in_row[j]    (computed rows)
 //   out_row    = in_row[j]                       (copy rows, copy_off[j])

@@ -21,9 +21,13 @@
 
 #include "carbonado_hip_cread.h"
 #include "cread_device.hpp"
+#include "stream_rules.hpp"
 
 namespace chip {
 namespace cread {
+
+using rules::ranges_overlap;
+using rules::up16;
 
 constexpr uint64_t MAX_ITEMS = uint64_t(1) << 31;
 constexpr uint64_t MAX_WORK = uint64_t(1) << 31;
@@ -31,8 +35,6 @@ constexpr uint64_t MAX_OFF = uint64_t(1) << 53;
 constexpr uint64_t ENV_OVERHEAD = 97;  // eph_pub65 || nonce16 || tag16 in front of the ciphertext
 constexpr uint64_t HDR_LEN = 81;       // eph_pub65 || nonce16
 constexpr uint64_t HDR_PITCH = 96;     // a header's slot in the scratch
-
-inline uint64_t up16(uint64_t x) { return (x + 15) & ~uint64_t(15); }
 
 struct Layout {
     uint64_t items = 0, keys = 0, km = 0, total = 0;
@@ -61,18 +63,6 @@ struct Plan {
     uint32_t keys_used = 0;
     std::vector<uint8_t> table;  // items || keys: holds key bytes, the caller wipes it
 };
-
-// whether two of the non-empty ranges [off[i], off[i] + len[i]) overlap
-inline bool ranges_overlap(const uint64_t *off, const uint64_t *len, uint64_t count) {
-    std::vector<std::pair<uint64_t, uint64_t>> r;
-    r.reserve(count);
-    for (uint64_t i = 0; i < count; ++i)
-        if (len[i]) r.emplace_back(off[i], len[i]);
-    std::sort(r.begin(), r.end());
-    for (size_t i = 1; i < r.size(); ++i)
-        if (r[i - 1].first + r[i - 1].second > r[i].first) return true;
-    return false;
-}
 
 // The checks of chipc_ctr_ranges_dev and the call's table.  kill (optional, the
 // read): item i with kill[i] != 0 gets zeros and that status, and uses no key.

@@ -24,9 +24,13 @@
 
 #include "carbonado_hip_ecies.h"
 #include "gcm_device.hpp"
+#include "stream_rules.hpp"
 
 namespace chip {
 namespace ecies {
+
+using rules::ranges_overlap;
+using rules::up16;
 
 constexpr uint64_t MAX_COUNT = uint64_t(1) << 31;
 constexpr uint64_t MAX_MSG = (uint64_t(1) << 36) - 32;  // GCM's limit on one message
@@ -34,8 +38,6 @@ constexpr uint64_t MAX_ITEMS = uint64_t(1) << 31;
 constexpr uint64_t HDR_LEN = 81;    // eph_pub65 || nonce16 of an envelope
 constexpr uint64_t HDR_PITCH = 96;  // its slot in the scratch
 constexpr uint64_t ENV_OVERHEAD = 97;  // ... || tag16
-
-inline uint64_t up16(uint64_t x) { return (x + 15) & ~uint64_t(15); }
 
 struct Layout {
     uint64_t msgs = 0, hdrs = 0, keys = 0, km = 0, vals = 0, ok = 0, total = 0;
@@ -79,18 +81,6 @@ struct Plan {
     uint64_t count = 0, items = 0;
     std::vector<uint8_t> table;  // msgs || hdrs || keys: holds key bytes, the caller wipes it
 };
-
-// whether two of the non-empty ranges [base + off[o], + len[o]) overlap
-inline bool ranges_overlap(const uint64_t *off, const uint64_t *len, uint64_t count) {
-    std::vector<std::pair<uint64_t, uint64_t>> r;
-    r.reserve(count);
-    for (uint64_t o = 0; o < count; ++o)
-        if (len[o]) r.emplace_back(off[o], len[o]);
-    std::sort(r.begin(), r.end());
-    for (size_t i = 1; i < r.size(); ++i)
-        if (r[i - 1].first + r[i - 1].second > r[i].first) return true;
-    return false;
-}
 
 // The checks of chipe_gcm_seal_ragged_dev (seal) / chipe_gcm_open_ragged_dev
 // and the call's table.  d_plain is the side that wants 16-B alignment: the

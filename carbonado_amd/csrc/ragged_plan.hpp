@@ -5,15 +5,20 @@
 // program can exercise it under a sanitizer (tests/ragged_plan_check.cpp).
 #pragma once
 
-#include <algorithm>
 #include <cstdint>
-#include <utility>
 #include <vector>
 
 #include "../../include/carbonado_hip_ext.h"
+#include "stream_rules.hpp"
 
 namespace chip {
 namespace ragged {
+
+using rules::bao_content;
+using rules::bao_len;
+using rules::chunks;
+using rules::ranges_overlap;
+using rules::up;
 
 constexpr uint64_t MAX_OBJECT = uint64_t(16) << 20;  // per object; its Zfec|Bao stream is KM_MAX_N chunks
 constexpr uint64_t GROUP = 64;                      // chunks per workgroup of the group kernel
@@ -35,22 +40,7 @@ struct Obj {
 };
 static_assert(sizeof(Obj) == 64, "descriptor layout");
 
-inline uint64_t chunks(uint64_t n) { return n == 0 ? 1 : (n + 1023) / 1024; }
-inline uint64_t bao_len(uint64_t n) { return 8 + n + 64 * (chunks(n) - 1); }
 inline uint64_t shard_len(uint64_t n) { return (n + 4095) / 4096 * 1024; }  // utils.rs:47-58 at k = 4
-
-// content length of a bao stream of `len` bytes (false: no such stream)
-inline bool bao_content(uint64_t len, uint64_t *n) {
-    if (len < 8) return false;
-    uint64_t lo = 0, hi = len - 8;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (bao_len(mid) < len) lo = mid + 1;
-        else hi = mid;
-    }
-    *n = lo;
-    return bao_len(lo) == len;
-}
 
 inline bool device_format(uint8_t f) {
     return f == CHIP_FORMAT_BAO || f == CHIP_FORMAT_ZFEC || f == (CHIP_FORMAT_BAO | CHIP_FORMAT_ZFEC);
@@ -60,8 +50,6 @@ inline uint64_t encoded_len(uint8_t format, uint64_t n) {
     const uint64_t z = (format & CHIP_FORMAT_ZFEC) ? 8 * shard_len(n) : n;
     return (format & CHIP_FORMAT_BAO) ? bao_len(z) : z;
 }
-
-inline uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 // scratch: [objs | groups prefix | blocks prefix | group CVs], each on a 256-B boundary
 struct ScratchLayout {
@@ -102,18 +90,6 @@ inline int layout(uint8_t format, const uint64_t *n, uint64_t count, uint64_t al
     }
     *total = row;
     return CHIP_OK;
-}
-
-// true when two of the ranges [off[o], off[o] + len[o]) with len[o] > 0 share a byte
-inline bool ranges_overlap(const uint64_t *off, const uint64_t *len, uint64_t count) {
-    std::vector<std::pair<uint64_t, uint64_t>> r;
-    r.reserve(count);
-    for (uint64_t o = 0; o < count; ++o)
-        if (len[o]) r.emplace_back(off[o], len[o]);
-    std::sort(r.begin(), r.end());
-    for (size_t i = 1; i < r.size(); ++i)
-        if (r[i - 1].first + r[i - 1].second > r[i].first) return true;
-    return false;
 }
 
 inline int finish(Plan *p) {

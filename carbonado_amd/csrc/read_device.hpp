@@ -8,6 +8,39 @@
 namespace chip {
 namespace read {
 
+// A segment's own slice is authentic.  KD keeps one status word per slice; KV
+// splits the own slice's into a chunk word (rstat[g]) and a path word, and
+// either one set condemns it (PATH).
+template <bool PATH>
+__device__ __forceinline__ bool own_ok(const uint32_t *rstat, const uint32_t *pathw, uint32_t g) {
+    return (PATH ? rstat[g] | pathw[g] : rstat[g]) == 0;
+}
+
+// How segment g is served: direct when its own slice is authentic, else rebuilt
+// from the four lowest authentic shares among its 7 fallback words (the mask's
+// entry of the host-built table, row p of their inverse), else failed.
+template <bool PATH>
+__device__ __forceinline__ Served serve_segment(const Seg *segs, const MaskEntry *masks, const uint32_t *rstat,
+                                                const uint32_t *pathw, uint32_t nseg, uint32_t g) {
+    Served out = {DIRECT, 0u, 0u, 0u};
+    if (own_ok<PATH>(rstat, pathw, g)) return out;
+    const uint32_t p = segs[g].p;
+    uint32_t mask = 0;
+    for (uint32_t i = 0; i < M; ++i)
+        if (i != p && rstat[nseg + FALLBACKS * g + (i < p ? i : i - 1)] == 0) mask |= 1u << i;
+    const MaskEntry *e = masks + mask;  // read in place: no private copy indexed by p
+    if (!e->ok) {
+        out.mode = FAILED;
+        return out;
+    }
+    out.mode = REBUILT;
+    for (uint32_t s = 0; s < K; ++s) {
+        out.sel |= (uint32_t)e->sel[s] << (8 * s);
+        out.coef |= (uint32_t)e->coef[K * p + s] << (8 * s);
+    }
+    return out;
+}
+
 // segment g's own slice request moved to fallback k of its 7 (shard k below its primary p, k + 1 from it on)
 __device__ __forceinline__ audit::Req fallback_slice(audit::Req a, const Seg *segs, uint32_t g, uint32_t k) {
     const uint32_t p = segs[g].p, spc = segs[g].spc, shard = k < p ? k : k + 1;

@@ -13,7 +13,9 @@
 //    (audit_checks.hpp) over the fallback slices, GATED: a work item whose
 //    segment's primary status word is 0 returns before it loads a node, so an
 //    intact read hashes one window per segment and a damaged one eight.  The
-//    decision is the device's, there is no synchronisation in the call;
+//    decision is the device's, there is no synchronisation in the call.  The
+//    vouched reads (KV) launch the same pair with PATH set: their gate also
+//    reads the segment's path word;
 //  * read_resolve_kernel: one lane per request, over its at most 4 segments:
 //    8 status words -> direct (own slice authentic), rebuilt (the mask's entry
 //    of the host-built table: the four lowest authentic shares and row p of
@@ -46,26 +48,28 @@ using audit::TPB;
 static_assert(BLOCK == UNIT * TPB, "content bytes per workgroup");
 
 // items [fpar[g], fpar[g + 1]) are segment g's: 7 x the most parents any of its fallback slices selects
+template <bool PATH>
 __global__ __launch_bounds__(TPB) void read_fallback_parent_kernel(const audit::Req *slices, const Seg *segs,
                                                                    const uint64_t *fpar, uint32_t nseg, uint64_t total,
-                                                                   uint32_t *rstat) {
+                                                                   const uint32_t *pathw, uint32_t *rstat) {
     const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
     if (i >= total) return;
-    const uint32_t g = audit::find_req(fpar, nseg, i);
-    if (rstat[g] == 0) return;  // the segment's own slice is authentic
+    const uint32_t g = audit::prefix_find(fpar, nseg, i);
+    if (own_ok<PATH>(rstat, pathw, g)) return;
     fallback_parent_item(slices, segs, fpar, nseg, i, g, rstat);
 }
 
 // items [7 pre[g], 7 pre[g + 1]) are segment g's, pre = KA's chunk prefix of the primary slices
+template <bool PATH>
 __global__ __launch_bounds__(TPB) void read_fallback_chunk_kernel(const audit::Req *slices, const Seg *segs,
                                                                   const uint64_t *pre, uint32_t nseg, uint64_t total,
-                                                                  uint32_t *rstat) {
+                                                                  const uint32_t *pathw, uint32_t *rstat) {
     __shared__ __attribute__((aligned(16))) uint32_t msg[QUADS][16];  // each quad's message block
     const int t = threadIdx.x;
     const uint64_t i = (uint64_t)blockIdx.x * QUADS + (t >> 2);
     if (i >= total) return;  // whole quads leave; the kernel has no workgroup barrier
-    const uint32_t g = audit::find_req(pre, nseg, i / FALLBACKS);
-    if (rstat[g] == 0) return;
+    const uint32_t g = audit::prefix_find(pre, nseg, i / FALLBACKS);
+    if (own_ok<PATH>(rstat, pathw, g)) return;
     fallback_chunk_item(slices, segs, pre, nseg, i, g, rstat, msg, t);
 }
 
@@ -77,42 +81,16 @@ __global__ __launch_bounds__(TPB) void read_resolve_kernel(const Req *reqs, cons
     const Req q = reqs[r];
     uint32_t st = q.status, bits = 0;
     for (uint32_t k = 0; k < q.nseg; ++k) {
-        const uint32_t g = q.seg0 + k, p = segs[g].p;
-        Served out = {DIRECT, 0u, 0u, 0u};
-        if (rstat[g] == 0) {
-            bits |= 1u << p;
-        } else {
-            uint32_t mask = 0;
-            for (uint32_t i = 0; i < M; ++i)
-                if (i != p && rstat[nseg + FALLBACKS * g + (i < p ? i : i - 1)] == 0) mask |= 1u << i;
-            const MaskEntry *e = masks + mask;  // read in place: no private copy indexed by p
-            if (e->ok) {
-                out.mode = REBUILT;
-                for (uint32_t s = 0; s < K; ++s) {
-                    out.sel |= (uint32_t)e->sel[s] << (8 * s);
-                    out.coef |= (uint32_t)e->coef[K * p + s] << (8 * s);
-                    bits |= 1u << e->sel[s];
-                }
-            } else {
-                out.mode = FAILED;
-                st = CHIP_ERR_ZFEC;
-            }
-        }
+        const uint32_t g = q.seg0 + k;
+        const Served out = serve_segment<false>(segs, masks, rstat, nullptr, nseg, g);
+        if (out.mode == DIRECT) bits |= 1u << segs[g].p;
+        else if (out.mode == FAILED) st = CHIP_ERR_ZFEC;
+        else
+            for (uint32_t s = 0; s < K; ++s) bits |= 1u << (out.sel >> (8 * s) & 0xFFu);
         served[g] = out;
     }
     status[r] = st;
     used[r] = st ? 0u : bits;
-}
-
-// the segment of workgroup b: pre[g] <= b < pre[g + 1] (pre[0] = 0, pre[nseg] = gridDim.x)
-__device__ __forceinline__ uint32_t find_seg(const uint64_t *pre, uint32_t nseg, uint64_t b) {
-    uint32_t lo = 0, hi = nseg;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // Bytes [col, col + nv) of the shard whose chunks start at chunk `ch0` of the
@@ -145,7 +123,7 @@ __device__ __forceinline__ u32x4 gather16(const uint8_t *src, uint64_t ch0, uint
 __global__ __launch_bounds__(TPB) void read_kernel(const Seg *segs, const uint64_t *blocks, uint32_t nseg,
                                                    const Served *served, const uint32_t *status) {
     __shared__ uint32_t tab[256];
-    const uint32_t g = find_seg(blocks, nseg, blockIdx.x);
+    const uint32_t g = audit::prefix_find<uint64_t>(blocks, nseg, blockIdx.x);
     const Seg a = segs[g];
     const Served how = served[g];
     const uint32_t mode = status[a.req] ? (uint32_t)FAILED : how.mode;  // uniform in the workgroup
@@ -195,20 +173,22 @@ __global__ __launch_bounds__(TPB) void read_kernel(const Seg *segs, const uint64
     else store16_partial(dst, out, nv);
 }
 
-inline unsigned nblocks(uint64_t items, uint64_t per) { return (unsigned)((items + per - 1) / per); }
-
 }  // namespace read
 
-hipError_t read_fallback_launch(const ReadLaunch &L, hipStream_t stream) {
+hipError_t read_fallback_launch(const ReadLaunch &L, const uint32_t *pathw, hipStream_t stream) {
     using namespace read;
     const uint32_t nseg = (uint32_t)L.nseg;
     const uint64_t fb_chunks = FALLBACKS * L.prim_chunks;
-    if (L.fb_parents)
-        hipLaunchKernelGGL(read_fallback_parent_kernel, dim3(nblocks(L.fb_parents, TPB)), dim3(TPB), 0, stream, L.slices,
-                           L.segs, L.fpar, nseg, L.fb_parents, L.rstat);
-    if (fb_chunks)
-        hipLaunchKernelGGL(read_fallback_chunk_kernel, dim3(nblocks(fb_chunks, QUADS)), dim3(TPB), 0, stream, L.slices,
-                           L.segs, L.chunks, nseg, fb_chunks, L.rstat);
+    if (L.fb_parents) {
+        const auto k = pathw ? read_fallback_parent_kernel<true> : read_fallback_parent_kernel<false>;
+        hipLaunchKernelGGL(k, dim3(nblocks(L.fb_parents, TPB)), dim3(TPB), 0, stream, L.slices, L.segs, L.fpar, nseg,
+                           L.fb_parents, pathw, L.rstat);
+    }
+    if (fb_chunks) {
+        const auto k = pathw ? read_fallback_chunk_kernel<true> : read_fallback_chunk_kernel<false>;
+        hipLaunchKernelGGL(k, dim3(nblocks(fb_chunks, QUADS)), dim3(TPB), 0, stream, L.slices, L.segs, L.chunks, nseg,
+                           fb_chunks, pathw, L.rstat);
+    }
     return hipGetLastError();
 }
 

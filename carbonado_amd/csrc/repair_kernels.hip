@@ -39,27 +39,6 @@ namespace repair {
 constexpr int TPB = 256;
 static_assert(BLOCK == 16 * TPB, "bytes of a share per workgroup");
 
-// the repair of workgroup b: pre[r] <= b < pre[r + 1] (pre[0] = 0, pre[nrep] = gridDim.x)
-__device__ __forceinline__ uint32_t find_rep(const uint32_t *pre, uint32_t nrep, uint32_t b) {
-    uint32_t lo = 0, hi = nrep;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t find_rep64(const uint64_t *pre, uint32_t nrep, uint64_t i) {
-    uint32_t lo = 0, hi = nrep;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // 16 B of the four output rows from 16 B at the same position of each input
 // (ragged_kernels.hip parity16: the packed table in LDS, a 4 x 4 transpose)
 __device__ __forceinline__ void product16(const uint32_t *tab, const u32x4 (&v)[4], u32x4 (&p)[4]) {
@@ -84,7 +63,7 @@ __device__ __forceinline__ void product16(const uint32_t *tab, const u32x4 (&v)[
 
 __global__ __launch_bounds__(TPB) void repair_decode_kernel(const Rec *recs, const uint32_t *blocks, uint32_t nrep) {
     __shared__ uint32_t tab[4 * 256];
-    const uint32_t rep = find_rep(blocks, nrep, blockIdx.x);
+    const uint32_t rep = audit::prefix_find<uint32_t>(blocks, nrep, blockIdx.x);
     const Rec a = recs[rep];
     const uint32_t x = threadIdx.x;
 #pragma unroll
@@ -139,7 +118,7 @@ __global__ __launch_bounds__(TPB) void repair_commit_kernel(const Commit *commit
                                                             uint64_t total, const uint32_t *ok) {
     const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
     if (i >= total) return;
-    const uint32_t j = find_rep64(pre, nrep, i);
+    const uint32_t j = audit::prefix_find(pre, nrep, i);
     if (!ok[j]) return;
     const Commit a = commits[j];
     const uint64_t o = UNIT * (i - pre[j]), left = a.len - o;  // a multiple of 8
@@ -149,15 +128,14 @@ __global__ __launch_bounds__(TPB) void repair_commit_kernel(const Commit *commit
     else store8<false>(out, *reinterpret_cast<const u32x2 *>(row));
 }
 
-inline unsigned nblocks(uint64_t items) { return (unsigned)((items + TPB - 1) / TPB); }
-
 }  // namespace repair
 
 hipError_t repair_fold_launch(const uint32_t *rstat, const uint32_t *first, uint32_t count, uint32_t *masks,
                               hipStream_t stream) {
     using namespace repair;
     if (count)
-        hipLaunchKernelGGL(repair_fold_kernel, dim3(nblocks(count)), dim3(TPB), 0, stream, rstat, first, count, masks);
+        hipLaunchKernelGGL(repair_fold_kernel, dim3(nblocks(count, TPB)), dim3(TPB), 0, stream, rstat, first, count,
+                           masks);
     return hipGetLastError();
 }
 
@@ -173,10 +151,10 @@ hipError_t repair_commit_launch(const repair::Commit *commits, const uint64_t *u
                                 uint64_t total_units, uint32_t *ok, hipStream_t stream) {
     using namespace repair;
     if (!nrep) return hipSuccess;
-    hipLaunchKernelGGL(repair_compare_kernel, dim3(nblocks(nrep)), dim3(TPB), 0, stream, commits, nrep, ok);
+    hipLaunchKernelGGL(repair_compare_kernel, dim3(nblocks(nrep, TPB)), dim3(TPB), 0, stream, commits, nrep, ok);
     if (total_units)
-        hipLaunchKernelGGL(repair_commit_kernel, dim3(nblocks(total_units)), dim3(TPB), 0, stream, commits, units, nrep,
-                           total_units, ok);
+        hipLaunchKernelGGL(repair_commit_kernel, dim3(nblocks(total_units, TPB)), dim3(TPB), 0, stream, commits, units,
+                           nrep, total_units, ok);
     return hipGetLastError();
 }
 

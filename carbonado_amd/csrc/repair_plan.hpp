@@ -29,7 +29,7 @@ constexpr uint64_t UNIT = 16;          // bytes per work item of the commit gath
 constexpr uint64_t ROW_OFFSET = 56;    // a staged row's stream: every chunk and node on a 64-B boundary
 constexpr uint32_t K = 4, M = 8;
 
-inline uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+using rules::up;
 
 // One stream to repair, as repair_decode_kernel reads it (device scratch).
 struct Rec {
@@ -208,19 +208,13 @@ inline int plan_verdicts(uintptr_t d_in, const uint64_t *in_off, const std::vect
 }
 
 // What scrub decides for a stream from its mask before any repair work
-// (chip_scrub_batch_dev's order): a status, or -1 = repair it.
+// (chip_scrub_batch_dev's order): a status, or rules::REPAIR.
 inline int pre_status(uint64_t in_len, uint64_t n, uint32_t chunk_len, uint32_t padding, uint32_t mask) {
     const uint64_t C = shard_len_of(n, chunk_len);
     if (!C) return CHIP_ERR_ZFEC;
     const int good = __builtin_popcount(mask & 0xFFu);
     if (good == (int)M) return CHIP_ERR_UNNECESSARY_SCRUB;  // decoding.rs:169-170
-    if (good < (int)K) return CHIP_ERR_ZFEC;                // zfec_chunks: too few shares
-    const uint64_t kc = K * C;
-    if (padding > kc) return CHIP_ERR_ZFEC;
-    const uint64_t n2 = kc - padding, target = up(n2, 1024 * K);  // utils.rs:47-58
-    if (target - n2 != padding) return CHIP_ERR_SCRUBBED_PADDING_MISMATCH;
-    if (audit::bao_len(M * (target / K)) != in_len) return CHIP_ERR_SCRUBBED_LENGTH_MISMATCH;
-    return -1;
+    return rules::scrub_verdict(in_len, C, padding, (uint32_t)good);
 }
 
 // the 16 coefficients of a record: the inverse of rows sel[0..4) of zfec_enc_matrix(4, 8)

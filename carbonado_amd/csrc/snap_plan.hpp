@@ -13,9 +13,13 @@
 
 #include "../../include/carbonado_hip.h"
 #include "snap_device.hpp"
+#include "stream_rules.hpp"
 
 namespace chip {
 namespace snap {
+
+using rules::ranges_overlap;
+using rules::up16;
 
 constexpr uint64_t MAX_COUNT = uint64_t(1) << 31;
 constexpr uint64_t MAX_LEN = uint64_t(1) << 40;     // an object, a stream or a capacity
@@ -23,24 +27,11 @@ constexpr uint64_t MAX_OFFSET = uint64_t(1) << 53;
 constexpr uint64_t MAX_ITEMS = uint64_t(1) << 31;   // blocks (compress) or slots (decompress) of a call
 constexpr uint64_t STREAM_ID_LEN = 10;
 
-inline uint64_t up16(uint64_t x) { return (x + 15) / 16 * 16; }
 inline uint64_t blocks_of(uint64_t n) { return (n + MAX_BLOCK - 1) / MAX_BLOCK; }
 // chip_snap_max_len
 inline uint64_t max_len(uint64_t n) { return n == 0 ? 0 : STREAM_ID_LEN + 8 * blocks_of(n) + n; }
 // data chunks a stream may have: every stream FrameEncoder or this library writes fits
 inline uint64_t slots_of(uint64_t out_cap) { return blocks_of(out_cap) + 1; }
-
-// true when two of the ranges [off[o], off[o] + len[o]) with len[o] > 0 share a byte
-inline bool ranges_overlap(const uint64_t *off, const uint64_t *len, uint64_t count) {
-    std::vector<std::pair<uint64_t, uint64_t>> r;
-    r.reserve(count);
-    for (uint64_t o = 0; o < count; ++o)
-        if (len[o]) r.emplace_back(off[o], len[o]);
-    std::sort(r.begin(), r.end());
-    for (size_t i = 1; i < r.size(); ++i)
-        if (r[i - 1].first + r[i - 1].second > r[i].first) return true;
-    return false;
-}
 
 // ---- compress: [objs | blks] uploaded, then [meta | slots]
 struct CLayout {

@@ -6,11 +6,11 @@
 // each segment, KA's chunk kernel into its CHUNK word (rstat[g], where KD keeps
 // its one word); a slice is authentic when both are 0.  Then
 //
-//  * vread_fallback_parent_kernel / vread_fallback_chunk_kernel: KD's gated
-//    checks of the 7 fallback slices, the gate reading "either word set";
-//  * vread_resolve_kernel: one lane per segment: direct, rebuilt (the mask
-//    table's entry: the four lowest authentic shares and row p of their
-//    inverse) or failed, as KD's resolve decides it;
+//  * KD's gated checks of the 7 fallback slices (read_kernels.hip:
+//    read_fallback_parent_kernel / read_fallback_chunk_kernel), launched with
+//    the gate that reads "either word set";
+//  * vread_resolve_kernel: one lane per segment: direct, rebuilt or failed, by
+//    KD's own decision (read_device.hpp: serve_segment);
 //  * vread_vouch_kernel, the new hot part: one QUAD of lanes per (segment,
 //    window chunk), found through KA's chunk prefix of the primary slices.
 //    GATED on the segment: only mode REBUILT under a path word of 0 runs; every
@@ -46,62 +46,15 @@ namespace vread {
 
 using audit::QUADS;
 using audit::TPB;
-using read::FALLBACKS;
 using read::K;
 using read::M;
-
-// a segment's own slice is authentic: neither its chunk word nor its path word is set
-__device__ __forceinline__ bool own_ok(const uint32_t *rstat, const uint32_t *pathw, uint32_t g) {
-    return (rstat[g] | pathw[g]) == 0;
-}
-
-// items [fpar[g], fpar[g + 1]) are segment g's: 7 x the most parents any of its fallback slices selects
-__global__ __launch_bounds__(TPB) void vread_fallback_parent_kernel(const audit::Req *slices, const read::Seg *segs,
-                                                                    const uint64_t *fpar, uint32_t nseg, uint64_t total,
-                                                                    const uint32_t *pathw, uint32_t *rstat) {
-    const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= total) return;
-    const uint32_t g = audit::find_req(fpar, nseg, i);
-    if (own_ok(rstat, pathw, g)) return;
-    read::fallback_parent_item(slices, segs, fpar, nseg, i, g, rstat);
-}
-
-// items [7 pre[g], 7 pre[g + 1]) are segment g's, pre = KA's chunk prefix of the primary slices
-__global__ __launch_bounds__(TPB) void vread_fallback_chunk_kernel(const audit::Req *slices, const read::Seg *segs,
-                                                                   const uint64_t *pre, uint32_t nseg, uint64_t total,
-                                                                   const uint32_t *pathw, uint32_t *rstat) {
-    __shared__ __attribute__((aligned(16))) uint32_t msg[QUADS][16];  // each quad's message block
-    const int t = threadIdx.x;
-    const uint64_t i = (uint64_t)blockIdx.x * QUADS + (t >> 2);
-    if (i >= total) return;  // whole quads leave; the kernel has no workgroup barrier
-    const uint32_t g = audit::find_req(pre, nseg, i / FALLBACKS);
-    if (own_ok(rstat, pathw, g)) return;
-    read::fallback_chunk_item(slices, segs, pre, nseg, i, g, rstat, msg, t);
-}
 
 __global__ __launch_bounds__(TPB) void vread_resolve_kernel(const read::Seg *segs, const read::MaskEntry *masks,
                                                             const uint32_t *rstat, const uint32_t *pathw, uint32_t nseg,
                                                             read::Served *served) {
     const uint32_t g = blockIdx.x * TPB + threadIdx.x;
     if (g >= nseg) return;
-    read::Served out = {read::DIRECT, 0u, 0u, 0u};
-    if (!own_ok(rstat, pathw, g)) {
-        const uint32_t p = segs[g].p;
-        uint32_t mask = 0;
-        for (uint32_t i = 0; i < M; ++i)
-            if (i != p && rstat[nseg + FALLBACKS * g + (i < p ? i : i - 1)] == 0) mask |= 1u << i;
-        const read::MaskEntry *e = masks + mask;  // read in place: no private copy indexed by p
-        if (e->ok) {
-            out.mode = read::REBUILT;
-            for (uint32_t s = 0; s < K; ++s) {
-                out.sel |= (uint32_t)e->sel[s] << (8 * s);
-                out.coef |= (uint32_t)e->coef[K * p + s] << (8 * s);
-            }
-        } else {
-            out.mode = read::FAILED;
-        }
-    }
-    served[g] = out;
+    served[g] = read::serve_segment<true>(segs, masks, rstat, pathw, nseg, g);
 }
 
 // sum_s coef[s] * x[s] on four packed bytes; mk[s][k] = all ones where bit k of coef[s] is set
@@ -122,7 +75,7 @@ __global__ __launch_bounds__(TPB) void vread_vouch_kernel(const audit::Req *slic
     const int t = threadIdx.x, q = t & 3, qd = t >> 2;
     const uint64_t i = (uint64_t)blockIdx.x * QUADS + qd;
     if (i >= total) return;  // whole quads leave; the kernel has no workgroup barrier
-    const uint32_t g = audit::find_req(pre, nseg, i);
+    const uint32_t g = audit::prefix_find(pre, nseg, i);
     const read::Served how = served[g];
     if (how.mode != read::REBUILT || pathw[g] != 0) return;  // nothing to vouch for, or nothing to compare with
     const audit::Req a = slices[g];
@@ -201,23 +154,7 @@ __global__ __launch_bounds__(TPB) void vread_finish_kernel(const read::Req *reqs
     vouch[r] = v;
 }
 
-inline unsigned nblocks(uint64_t items, uint64_t per) { return (unsigned)((items + per - 1) / per); }
-
 }  // namespace vread
-
-hipError_t vread_fallback_launch(const VreadLaunch &L, hipStream_t stream) {
-    using namespace vread;
-    const ReadLaunch &R = L.rd;
-    const uint32_t nseg = (uint32_t)R.nseg;
-    const uint64_t fb_chunks = FALLBACKS * R.prim_chunks;
-    if (R.fb_parents)
-        hipLaunchKernelGGL(vread_fallback_parent_kernel, dim3(nblocks(R.fb_parents, TPB)), dim3(TPB), 0, stream,
-                           R.slices, R.segs, R.fpar, nseg, R.fb_parents, L.pathw, R.rstat);
-    if (fb_chunks)
-        hipLaunchKernelGGL(vread_fallback_chunk_kernel, dim3(nblocks(fb_chunks, QUADS)), dim3(TPB), 0, stream, R.slices,
-                           R.segs, R.chunks, nseg, fb_chunks, L.pathw, R.rstat);
-    return hipGetLastError();
-}
 
 hipError_t vread_vouch_launch(const VreadLaunch &L, hipStream_t stream) {
     using namespace vread;

@@ -18,12 +18,8 @@ struct VreadLaunch {
     uint32_t strict;   // flags & CHIPV_STRICT
 };
 
-// Enqueue the fallback slices' checks, each gated on its segment's two words
-// (two launches, behind KA's two checks of the primary slices).
-hipError_t vread_fallback_launch(const VreadLaunch &L, hipStream_t stream);
-
 // Enqueue the class per segment and the gated hashing of the rebuilt window
-// chunks (two launches).
+// chunks (two launches, behind read_fallback_launch with the path words).
 hipError_t vread_vouch_launch(const VreadLaunch &L, hipStream_t stream);
 
 // Enqueue the verdict per request: status, used and vouch (one launch).  The

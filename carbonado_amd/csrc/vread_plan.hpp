@@ -36,18 +36,6 @@ struct ScratchLayout {
 
 inline uint64_t scratch_len(uint64_t nreq, uint64_t nseg) { return ScratchLayout(nreq, nseg).total; }
 
-// the segment of vouch item i: pre[g] <= i < pre[g + 1] (pre[0] = 0, pre[nseg] > i;
-// segments are never empty, so neither is a window).  audit::find_req on the host.
-inline uint32_t item_segment(const uint64_t *pre, uint32_t nseg, uint64_t i) {
-    uint32_t lo = 0, hi = nseg;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pre[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 struct Plan {
     read::Plan rd;
     ScratchLayout lay{0, 0};

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <utility>
 #include <vector>
 
 #include "../carbonado_amd/csrc/audit_plan.hpp"
@@ -108,8 +109,56 @@ static void check_request(uint64_t n, uint64_t index, uint64_t count) {
     EXPECT(sel.olen == (start < n ? umin(n, start + count * 1024) - start : 0));
 }
 
+// ranges_overlap against every pair compared: seeded sets of up to 12 ranges that
+// tile a line with gaps (so neighbours touch or stand apart), some of them empty
+// and lying anywhere, in ascending or shuffled order, with or without one range
+// stretched into its successor, which is also placed at the last pair
+static bool overlap_plain(const std::vector<uint64_t> &off, const std::vector<uint64_t> &len) {
+    for (size_t a = 0; a < off.size(); ++a)
+        for (size_t b = a + 1; b < off.size(); ++b)
+            if (len[a] && len[b] && off[a] < off[b] + len[b] && off[b] < off[a] + len[a]) return true;
+    return false;
+}
+
+static void check_overlaps(std::mt19937_64 &rng) {
+    int seen[2][2] = {{0, 0}, {0, 0}};  // [shuffled][overlapping]
+    for (int round = 0; round < 400; ++round) {
+        const size_t count = rng() % 13;
+        std::vector<uint64_t> off(count), len(count);
+        uint64_t cur = rng() % 64;
+        for (size_t r = 0; r < count; ++r) {
+            off[r] = cur;
+            len[r] = rng() % 4 == 0 ? 0 : 1 + rng() % 100;  // zero-length members
+            cur += len[r] + (rng() % 2 ? 0 : rng() % 50);   // touching, or a gap
+            if (!len[r] && rng() % 2) off[r] = rng() % (cur + 1);  // an empty range overlaps nothing, wherever it lies
+        }
+        std::vector<size_t> full;
+        for (size_t r = 0; r < count; ++r)
+            if (len[r]) full.push_back(r);
+        const int kind = round % 3;  // 0: disjoint, 1: one overlap somewhere, 2: one overlap at the last pair
+        if (kind && full.size() >= 2) {
+            const size_t at = kind == 2 ? full.size() - 2 : rng() % (full.size() - 1);
+            len[full[at]] = off[full[at + 1]] - off[full[at]] + 1 + rng() % 3;
+        }
+        const bool shuffled = round % 2;
+        if (shuffled)
+            for (size_t r = count; r > 1; --r) {
+                const size_t j = rng() % r;
+                std::swap(off[r - 1], off[j]);
+                std::swap(len[r - 1], len[j]);
+            }
+        const bool want = overlap_plain(off, len);
+        EXPECT(want == (kind && full.size() >= 2));
+        EXPECT(ranges_overlap(off.data(), len.data(), count) == want);
+        ++seen[shuffled][want];
+    }
+    EXPECT(seen[0][0] > 20 && seen[0][1] > 20 && seen[1][0] > 20 && seen[1][1] > 20);
+    EXPECT(!ranges_overlap(nullptr, nullptr, 0));
+}
+
 static int plan_mode(unsigned seed) {
-    std::mt19937_64 rng(seed);
+    std::mt19937_64 rng(seed), own(seed ^ 0x0FF5E7u);  // (the mixes below keep their sequence)
+    check_overlaps(own);
     const uintptr_t STREAMS = 0x10000000, PROOFS = 0x400000000, CONTENT = 0x800000000, HASH = 0x70000000;
     EXPECT(select(0, MAX_SLICE, MAX_SLICE).olen == 0);  // the largest request wraps nowhere
     EXPECT(select(MAX_CONTENT, MAX_SLICE, MAX_SLICE).last == chunks(MAX_CONTENT));

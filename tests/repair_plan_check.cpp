@@ -80,6 +80,44 @@ static void check_statuses() {
     EXPECT(pre_status(len, n, C, 0, 0xFE) == -1 && pre_status(len, n, C, 4095, 0xFE) == -1);
 }
 
+// the verdicts behind the mask in their order: too few shares, padding out of
+// range, padding mismatch, length mismatch, and only then a repair; an earlier
+// cause hides every later one
+static void check_verdicts() {
+    using chip::rules::REPAIR;
+    using chip::rules::scrub_verdict;
+    int cases = 0;
+    for (uint64_t spc : {1, 2, 3, 7, 64, 1000})
+        for (uint32_t pad : {0u, 1u, 40u, 4095u}) {
+            const uint64_t C = 1024 * spc, len = audit::bao_len(8 * C);
+            const uint64_t other[3] = {len + 8, len - 8, audit::bao_len(8 * (C + 1024))};  // not this stream's length
+            const uint32_t off_range[2] = {(uint32_t)(4 * C + 1), ~0u};                     // padding > 4 C
+            const uint32_t mismatch[3] = {pad + 4096, (uint32_t)(4 * C), pad + 8192};        // <= 4 C, not what zfec pads
+            for (uint32_t good = 0; good <= 8; ++good) {
+                const bool few = good < 4;
+                EXPECT(scrub_verdict(len, C, pad, good) == (few ? CHIP_ERR_ZFEC : REPAIR));
+                for (uint32_t bad : off_range) {
+                    EXPECT(scrub_verdict(len, C, bad, good) == CHIP_ERR_ZFEC);
+                    for (uint64_t l : other) EXPECT(scrub_verdict(l, C, bad, good) == CHIP_ERR_ZFEC);
+                }
+                for (uint32_t bad : mismatch) {
+                    if (bad > 4 * C) continue;  // (one chunk per shard: the larger ones are out of range instead)
+                    const int want = few ? CHIP_ERR_ZFEC : CHIP_ERR_SCRUBBED_PADDING_MISMATCH;
+                    EXPECT(scrub_verdict(len, C, bad, good) == want);
+                    for (uint64_t l : other) EXPECT(scrub_verdict(l, C, bad, good) == want);
+                }
+                for (uint64_t l : other)
+                    EXPECT(scrub_verdict(l, C, pad, good) == (few ? CHIP_ERR_ZFEC : CHIP_ERR_SCRUBBED_LENGTH_MISMATCH));
+                ++cases;
+            }
+            // what pre_status decides in front of them, and that it hands the rest on unchanged
+            EXPECT(pre_status(len, 8 * C, (uint32_t)C, pad, 0xFF) == CHIP_ERR_UNNECESSARY_SCRUB);
+            EXPECT(pre_status(len + 8, 8 * C, (uint32_t)C, pad, 0x3C) == CHIP_ERR_SCRUBBED_LENGTH_MISMATCH);
+            EXPECT(pre_status(len + 8, 8 * C, (uint32_t)C + 1024, pad, 0x3C) == CHIP_ERR_ZFEC);
+        }
+    EXPECT(cases == 6 * 4 * 9);
+}
+
 static void check_overlaps() {
     const uintptr_t IN = 0x10000000, OUT = 0x80000000;
     const uint64_t len[2] = {audit::bao_len(8192), audit::bao_len(16384)};
@@ -102,6 +140,7 @@ int main(int argc, char **argv) {
     std::mt19937_64 rng(seed);
     check_inverses();
     check_statuses();
+    check_verdicts();
     check_overlaps();
     const uintptr_t IN = 0x10000000, OUT = 0x4000000000, HASH = 0x70000000, SCR = 0x7800000000;
     for (int round = 0; round < 120; ++round) {

@@ -4,15 +4,13 @@ the oracle's slices, the argument errors an audit call decides before it
 touches a device, and the host logic and item-to-node arithmetic behind them
 as a stand-alone program under ASan + UBSan."""
 import ctypes
-import os
 import random
 import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import pytest
 
+import boundary as B
 import test_rust_shim as RS
 from test_slice_verify import _grid
 from carbonado_amd import _lib
@@ -29,57 +27,23 @@ OK, INVALID_ARG, HASH_DECODE, TRUNCATED, NO_DEVICE = 0, 1, 4, 6, 100
 
 
 def audit_prototypes() -> dict:
-    text = RS._strip_comments(AUDIT_HEADER.read_text())
-    protos = {}
-    for ret, name, params in re.findall(r"CHIPA_API\s+([^;{}()]*?)\b(chipa_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
-        ps = []
-        params = " ".join(params.split())
-        if params and params != "void":
-            for p in params.split(","):
-                m = re.match(r"(.*?)(\w+)$", p.strip())
-                ps.append((m.group(2), RS.c_to_rust(m.group(1))))
-        protos[name] = (RS.c_to_rust(ret), ps)
-    return protos
-
-
-def _exported() -> set:
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    return {line.split()[-1] for line in out.splitlines() if " T " in line}
+    return B.prototypes(AUDIT_HEADER, "chipa_")
 
 
 def test_audit_exports_header_and_ctypes_are_one_set():
     protos = audit_prototypes()
     assert len(protos) == 6
-    exported = _exported()
-    assert set(protos) == {s for s in exported if s.startswith("chipa_")} == set(_lib.AUDIT_SIGNATURES)
-    for name, (_, ps) in protos.items():
-        assert len(_lib.AUDIT_SIGNATURES[name][1]) == len(ps), name
+    exported = B.exported()
+    B.assert_one_set(protos, exported, "chipa_")
     assert _lib.lib().chipa_abi_version() == 1
     assert "#define CHIPA_ABI_VERSION 1" in AUDIT_HEADER.read_text()
     # the two older boundaries keep their sets
-    assert len({s for s in exported if s.startswith("chip_")}) == 62
-    assert len({s for s in exported if s.startswith("chipx_")}) == 5
-    assert not set(_lib.AUDIT_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES))
+    B.assert_older_keep_their_sets(exported, "chipa_")
 
 
 def test_ffi_audit_declares_every_prototype_with_matching_types():
-    text = RS._strip_comments(FFI_AUDIT.read_text())
-    decls = {}
-    for block in re.findall(r'extern\s+"C"\s*\{(.*?)\n\}', text, flags=re.S):
-        for name, params, ret in re.findall(r"pub\s+fn\s+(chipa_\w+)\s*\(([^)]*)\)\s*(?:->\s*([^;]+?))?\s*;", block,
-                                            flags=re.S):
-            assert name not in decls
-            ps = [tuple(" ".join(s.split()) for s in p.split(":", 1))
-                  for p in filter(None, (x.strip() for x in " ".join(params.split()).split(",")))]
-            decls[name] = (" ".join(ret.split()) if ret else "", ps)
-    protos = audit_prototypes()
-    assert set(decls) == set(protos)
-    for name, (cret, cps) in protos.items():
-        rret, rps = decls[name]
-        assert cret == rret, name
-        assert [t for _, t in cps] == [t for _, t in rps], name
-        assert [n for n, _ in cps] == [n for n, _ in rps], name
+    B.assert_ffi_matches(B.ffi_declarations(FFI_AUDIT, "chipa_"), audit_prototypes())
+    text = B.ffi_text(FFI_AUDIT)
     assert re.search(r"pub const CHIPA_ABI_VERSION: c_int = 1;", text)
 
 
@@ -243,22 +207,7 @@ def test_audit_scratch_len_covers_the_table():
 
 @pytest.fixture(scope="module")
 def plan_check(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("audit_asan") / "audit_plan_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", str(ROOT / "tests" / "audit_plan_check.cpp"), "-I" + str(ROOT / "include"),
-           "-o", str(exe)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
-    return exe
-
-
-def _run(exe, *args):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(exe), *args], capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout
+    return B.build_check(tmp_path_factory, "audit_plan_check.cpp")
 
 
 @pytest.mark.parametrize("seed", ["1", "0xBEEF"])
@@ -266,7 +215,7 @@ def test_audit_plan_under_asan_ubsan(plan_check, seed):
     """Checks, layout, request table and prefix arrays of an audit call are
     host code (audit_plan.hpp): a stand-alone program drives them over seeded
     mixes, and checks that every request's work items tile its proof."""
-    assert "0 failures" in _run(plan_check, "plan", seed)
+    assert "0 failures" in B.run_check(plan_check, "plan", seed)
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -279,7 +228,7 @@ def test_work_items_are_the_nodes_bao_slice_selects(plan_check, streams, n):
     _, enc, h = streams[n]
     memo = P.bao_prime(enc, h)
     grid = _grid(n)
-    out = _run(plan_check, "nodes", *[str(x) for i, c in grid for x in (n, i, c)])
+    out = B.run_check(plan_check, "nodes", *[str(x) for i, c in grid for x in (n, i, c)])
     reqs = []
     for line in out.splitlines():
         f = line.split()

@@ -7,9 +7,7 @@ cread_plan.hpp) as a stand-alone program under ASan + UBSan against EVP
 AES-256-GCM."""
 import ctypes
 import json
-import os
 import re
-import shutil
 import subprocess
 import sys
 from pathlib import Path
@@ -17,6 +15,7 @@ from pathlib import Path
 import pytest
 
 import test_read_cpu as RC
+import boundary as B
 import test_rust_shim as RS
 from carbonado_amd import _lib
 
@@ -28,41 +27,21 @@ LIB_RS = ROOT / "carbonado-hip" / "src" / "lib.rs"
 OK, INVALID_ARG, HASH_DECODE, TRUNCATED, ECIES, NO_DEVICE = 0, 1, 4, 6, 17, 100
 NAMES = {"chipc_abi_version", "chipc_ctr_scratch_len", "chipc_ctr_ranges_dev", "chipc_stream_keys_scratch_len",
          "chipc_stream_keys_dev", "chipc_read_layout", "chipc_read_scratch_len", "chipc_read_ranges_dev"}
-OLDER = (("chip_", 62), ("chipx_", 5), ("chipa_", 6), ("chipr_", 4), ("chipd_", 4), ("chipv_", 3), ("chipe_", 10),
-         ("chips_", 10))
 
 
 def prototypes() -> dict:
-    text = RS._strip_comments(HEADER.read_text())
-    protos = {}
-    for ret, name, params in re.findall(r"CHIPC_API\s+([^;{}()]*?)\b(chipc_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
-        ps = []
-        params = " ".join(params.split())
-        if params and params != "void":
-            for p in params.split(","):
-                m = re.match(r"(.*?)(\w+)$", p.strip())
-                ps.append((m.group(2), RS.c_to_rust(m.group(1))))
-        protos[name] = (RS.c_to_rust(ret), ps)
-    return protos
+    return B.prototypes(HEADER, "chipc_")
 
 
 def test_exports_header_and_ctypes_are_one_set():
     protos = prototypes()
     assert set(protos) == NAMES and len(NAMES) == 8
-    exported = RC._exported()
-    assert set(protos) == {s for s in exported if s.startswith("chipc_")} == set(_lib.CREAD_SIGNATURES)
-    for name, (_, ps) in protos.items():
-        assert len(_lib.CREAD_SIGNATURES[name][1]) == len(ps), name
+    exported = B.exported()
+    B.assert_one_set(protos, exported, "chipc_")
     assert _lib.lib().chipc_abi_version() == 1
     assert "#define CHIPC_ABI_VERSION 1" in HEADER.read_text()
     # the eight older boundaries keep their sets; "chipc_" is a prefix of none of theirs and none is a prefix of it
-    for prefix, n in OLDER:
-        assert len({s for s in exported if s.startswith(prefix)}) == n, prefix
-        assert not prefix.startswith("chipc_") and not "chipc_".startswith(prefix)
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.AUDIT_SIGNATURES) |
-              set(_lib.REPAIR_SIGNATURES) | set(_lib.READ_SIGNATURES) | set(_lib.VREAD_SIGNATURES) |
-              set(_lib.ECIES_SIGNATURES) | set(_lib.SNAP_SIGNATURES))
-    assert not set(_lib.CREAD_SIGNATURES) & others
+    B.assert_older_keep_their_sets(exported, "chipc_")
     # the argument lists the issue fixes
     assert [n for n, _ in protos["chipc_ctr_ranges_dev"][1]] == [
         "keys", "ivs", "nkeys", "item_key", "pos", "n", "nitems", "d_buf", "buf_off", "d_gate", "d_scratch",
@@ -81,22 +60,8 @@ def test_exports_header_and_ctypes_are_one_set():
 
 
 def test_ffi_cread_declares_every_prototype_with_matching_types():
-    text = RS._strip_comments(FFI.read_text())
-    decls = {}
-    for block in re.findall(r'extern\s+"C"\s*\{(.*?)\n\}', text, flags=re.S):
-        for name, params, ret in re.findall(r"pub\s+fn\s+(chipc_\w+)\s*\(([^)]*)\)\s*(?:->\s*([^;]+?))?\s*;", block,
-                                            flags=re.S):
-            assert name not in decls
-            ps = [tuple(" ".join(s.split()) for s in p.split(":", 1))
-                  for p in filter(None, (x.strip() for x in " ".join(params.split()).split(",")))]
-            decls[name] = (" ".join(ret.split()) if ret else "", ps)
-    protos = prototypes()
-    assert set(decls) == set(protos)
-    for name, (cret, cps) in protos.items():
-        rret, rps = decls[name]
-        assert cret == rret, name
-        assert [t for _, t in cps] == [t for _, t in rps], name
-        assert [n for n, _ in cps] == [n for n, _ in rps], name
+    B.assert_ffi_matches(B.ffi_declarations(FFI, "chipc_"), prototypes())
+    text = B.ffi_text(FFI)
     assert re.search(r"pub const CHIPC_ABI_VERSION: c_int = 1;", text)
 
 
@@ -328,14 +293,7 @@ def test_read_argument_errors_in_their_order():
 
 @pytest.fixture(scope="module")
 def cread_check(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("cread_asan") / "cread_device_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", str(ROOT / "tests" / "cread_device_check.cpp"), "-I" + str(ROOT / "include"),
-           "-o", str(exe), "-lcrypto"]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
-    return exe
+    return B.build_check(tmp_path_factory, "cread_device_check.cpp", libs=["crypto"])
 
 
 def test_cread_device_and_plan_under_asan_ubsan(cread_check):
@@ -345,11 +303,8 @@ def test_cread_device_and_plan_under_asan_ubsan(cread_check):
     and the span edges, positions around 8192, the lite key setup's J0 against
     its definition, the committed counter-wrap pair, killed items and the plan's
     checks."""
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(cread_check)], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert r.stdout.strip().splitlines()[-1] == "0 failures"
+    out = B.run_check(cread_check, timeout=300)
+    assert out.strip().splitlines()[-1] == "0 failures"
 
 
 def test_cread_bench_dry_run():

@@ -6,9 +6,7 @@ length, the bench tool's dry run, and the arithmetic and host logic
 under ASan + UBSan, linked with libcrypto."""
 import ctypes
 import json
-import os
 import re
-import shutil
 import subprocess
 import sys
 from pathlib import Path
@@ -16,6 +14,7 @@ from pathlib import Path
 import pytest
 
 import test_read_cpu as RC
+import boundary as B
 import test_rust_shim as RS
 from carbonado_amd import _lib
 
@@ -31,34 +30,18 @@ NAMES = {"chipe_abi_version", "chipe_gcm_scratch_len", "chipe_gcm_seal_ragged_de
 
 
 def prototypes() -> dict:
-    text = RS._strip_comments(HEADER.read_text())
-    protos = {}
-    for ret, name, params in re.findall(r"CHIPE_API\s+([^;{}()]*?)\b(chipe_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
-        ps = []
-        params = " ".join(params.split())
-        if params and params != "void":
-            for p in params.split(","):
-                m = re.match(r"(.*?)(\w+)$", p.strip())
-                ps.append((m.group(2), RS.c_to_rust(m.group(1))))
-        protos[name] = (RS.c_to_rust(ret), ps)
-    return protos
+    return B.prototypes(HEADER, "chipe_")
 
 
 def test_exports_header_and_ctypes_are_one_set():
     protos = prototypes()
     assert set(protos) == NAMES
-    exported = RC._exported()
-    assert set(protos) == {s for s in exported if s.startswith("chipe_")} == set(_lib.ECIES_SIGNATURES)
-    for name, (_, ps) in protos.items():
-        assert len(_lib.ECIES_SIGNATURES[name][1]) == len(ps), name
+    exported = B.exported()
+    B.assert_one_set(protos, exported, "chipe_")
     assert _lib.lib().chipe_abi_version() == 1
     assert "#define CHIPE_ABI_VERSION 1" in HEADER.read_text()
     # the six older boundaries keep their sets
-    for prefix, n in (("chip_", 62), ("chipx_", 5), ("chipa_", 6), ("chipr_", 4), ("chipd_", 4), ("chipv_", 3)):
-        assert len({s for s in exported if s.startswith(prefix)}) == n, prefix
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.AUDIT_SIGNATURES) |
-              set(_lib.REPAIR_SIGNATURES) | set(_lib.READ_SIGNATURES) | set(_lib.VREAD_SIGNATURES))
-    assert not set(_lib.ECIES_SIGNATURES) & others
+    B.assert_older_keep_their_sets(exported, "chipe_")
     # the argument lists the issue fixes
     assert [n for n, _ in protos["chipe_seal_ragged_dev"][1]] == [
         "pubkey", "pubkey_len", "inject", "d_in", "in_off", "n", "count", "d_out", "out_off", "d_scratch", "stream"]
@@ -82,22 +65,8 @@ def test_older_entry_points_still_refuse_the_ecies_bit():
 
 
 def test_ffi_ecies_declares_every_prototype_with_matching_types():
-    text = RS._strip_comments(FFI.read_text())
-    decls = {}
-    for block in re.findall(r'extern\s+"C"\s*\{(.*?)\n\}', text, flags=re.S):
-        for name, params, ret in re.findall(r"pub\s+fn\s+(chipe_\w+)\s*\(([^)]*)\)\s*(?:->\s*([^;]+?))?\s*;", block,
-                                            flags=re.S):
-            assert name not in decls
-            ps = [tuple(" ".join(s.split()) for s in p.split(":", 1))
-                  for p in filter(None, (x.strip() for x in " ".join(params.split()).split(",")))]
-            decls[name] = (" ".join(ret.split()) if ret else "", ps)
-    protos = prototypes()
-    assert set(decls) == set(protos)
-    for name, (cret, cps) in protos.items():
-        rret, rps = decls[name]
-        assert cret == rret, name
-        assert [t for _, t in cps] == [t for _, t in rps], name
-        assert [n for n, _ in cps] == [n for n, _ in rps], name
+    B.assert_ffi_matches(B.ffi_declarations(FFI, "chipe_"), prototypes())
+    text = B.ffi_text(FFI)
     assert re.search(r"pub const CHIPE_ABI_VERSION: c_int = 1;", text)
 
 
@@ -316,14 +285,7 @@ def test_scratch_length():
 
 @pytest.fixture(scope="module")
 def gcm_check(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("gcm_asan") / "gcm_device_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", str(ROOT / "tests" / "gcm_device_check.cpp"), "-I" + str(ROOT / "include"),
-           "-o", str(exe), "-lcrypto"]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
-    return exe
+    return B.build_check(tmp_path_factory, "gcm_device_check.cpp", libs=["crypto"])
 
 
 @pytest.mark.parametrize("args", [["1"], ["0xBEEF"], ["3", "big"]])
@@ -333,11 +295,7 @@ def test_gcm_device_and_plan_under_asan_ubsan(gcm_check, args):
     bit loop, the counter's wrap, byte-granular block moves, the plan, and
     whole messages walked lane by lane as the kernels split them against EVP
     (`big`: the 64-item boundary of the second level, +-1)."""
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(gcm_check)] + args, capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "0 failures" in r.stdout
+    assert "0 failures" in B.run_check(gcm_check, *args, timeout=300)
 
 
 def test_ecies_bench_dry_run():

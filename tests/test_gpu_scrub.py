@@ -143,3 +143,28 @@ def test_scrub_batch_matches_single(gpu, off):
         if st == 0:
             assert single == encs[o][0]
             assert bytes(out[o, off:off + L].cpu().numpy()) == encs[o][0]
+
+
+def test_scrub_of_an_intact_stream_with_a_misfit_chunk_len(gpu):
+    """What each call decides first for an intact stream scrubbed with
+    chunk_len = 0: chip_scrub verifies before it looks at chunk_len
+    (UnnecessaryScrub), chip_scrub_batch_dev refuses the chunk_len for the
+    whole call (ZfecError), and the ragged call makes it that object's status."""
+    import types
+    import torch
+    import carbonado_amd as ca
+    from carbonado_amd import device as D
+    from carbonado_amd.error import UnnecessaryScrub, ZfecError
+    enc, h, info = ca.encode(b"", _rnd(1, 1), 12)
+    misfit = types.SimpleNamespace(padding_len=info.padding_len, chunk_len=0)
+    with pytest.raises(UnnecessaryScrub):
+        ca.scrub(enc, h, misfit)
+    L = len(enc)
+    inp = torch.frombuffer(bytearray(enc), dtype=torch.uint8).cuda()
+    hashes = torch.frombuffer(bytearray(h), dtype=torch.uint8).cuda().reshape(1, 32)
+    out = torch.zeros(L, dtype=torch.uint8, device="cuda")
+    with pytest.raises(ZfecError):
+        D.scrub_batch(inp.reshape(1, L), L, hashes, info.padding_len, 0, out.reshape(1, L), D.scrub_scratch(L, 1))
+    status = D.scrub_ragged(inp, [0], [L], hashes, [info.padding_len], [0], out, [0], D.scrub_ragged_scratch([L]))
+    assert list(status) == [7]
+    assert not out.any()

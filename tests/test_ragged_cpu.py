@@ -4,13 +4,12 @@ against the oracle, the argument errors a ragged call decides before it
 touches a device, and the host logic behind them under ASan + UBSan."""
 import ctypes
 import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import pytest
 
 import test_abi
+import boundary as B
 import test_rust_shim as RS
 from carbonado_amd import _lib
 from oracle import oracle as O
@@ -27,28 +26,14 @@ OK, INVALID_ARG, UNEVEN = 0, 1, 3
 
 
 def ext_prototypes() -> dict:
-    text = RS._strip_comments(EXT_HEADER.read_text())
-    protos = {}
-    for ret, name, params in re.findall(r"CHIPX_API\s+([^;{}()]*?)\b(chipx_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
-        ps = []
-        params = " ".join(params.split())
-        if params and params != "void":
-            for p in params.split(","):
-                m = re.match(r"(.*?)(\w+)$", p.strip())
-                ps.append((m.group(2), RS.c_to_rust(m.group(1))))
-        protos[name] = (RS.c_to_rust(ret), ps)
-    return protos
+    return B.prototypes(EXT_HEADER, "chipx_")
 
 
 def test_ext_exports_header_and_ctypes_are_one_set():
     protos = ext_prototypes()
     assert len(protos) == 5
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert set(protos) == {s for s in exported if s.startswith("chipx_")} == set(_lib.EXT_SIGNATURES)
-    for name, (_, ps) in protos.items():
-        assert len(_lib.EXT_SIGNATURES[name][1]) == len(ps), name
+    exported = B.exported()
+    B.assert_one_set(protos, exported, "chipx_")
     L = _lib.lib()
     assert L.chipx_abi_version() == 1
     assert "#define CHIPX_ABI_VERSION 1" in EXT_HEADER.read_text()
@@ -57,31 +42,15 @@ def test_ext_exports_header_and_ctypes_are_one_set():
 def test_drop_in_boundary_is_unchanged():
     L = _lib.lib()
     assert L.chip_abi_version() == 5
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    chip = {s for s in exported if s.startswith("chip_")}
-    assert chip == test_abi.header_symbols() == set(_lib.SIGNATURES) and len(chip) == 62
-    assert not set(_lib.SIGNATURES) & set(_lib.EXT_SIGNATURES)
+    exported = B.exported()
+    chip = B.exports_of(exported, "chip_")
+    assert chip == test_abi.header_symbols() == set(_lib.SIGNATURES)
+    B.assert_older_keep_their_sets(exported, "chipx_")
 
 
 def test_ffi_ext_declares_every_prototype_with_matching_types():
-    text = RS._strip_comments(FFI_EXT.read_text())
-    decls = {}
-    for block in re.findall(r'extern\s+"C"\s*\{(.*?)\n\}', text, flags=re.S):
-        for name, params, ret in re.findall(r"pub\s+fn\s+(chipx_\w+)\s*\(([^)]*)\)\s*(?:->\s*([^;]+?))?\s*;", block,
-                                            flags=re.S):
-            assert name not in decls
-            ps = [tuple(" ".join(s.split()) for s in p.split(":", 1))
-                  for p in filter(None, (x.strip() for x in " ".join(params.split()).split(",")))]
-            decls[name] = (" ".join(ret.split()) if ret else "", ps)
-    protos = ext_prototypes()
-    assert set(decls) == set(protos)
-    for name, (cret, cps) in protos.items():
-        rret, rps = decls[name]
-        assert cret == rret, name
-        assert [t for _, t in cps] == [t for _, t in rps], name
-        assert [n for n, _ in cps] == [n for n, _ in rps], name
+    B.assert_ffi_matches(B.ffi_declarations(FFI_EXT, "chipx_"), ext_prototypes())
+    text = B.ffi_text(FFI_EXT)
     assert re.search(r"pub const CHIPX_ABI_VERSION: c_int = 1;", text)
 
 
@@ -184,23 +153,11 @@ def test_ragged_scratch_len_covers_the_tables():
 
 @pytest.fixture(scope="module")
 def plan_check(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("ragged_asan") / "ragged_plan_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", str(ROOT / "tests" / "ragged_plan_check.cpp"), "-I" + str(ROOT / "include"),
-           "-o", str(exe)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
-    return exe
+    return B.build_check(tmp_path_factory, "ragged_plan_check.cpp")
 
 
 @pytest.mark.parametrize("seed", ["1", "0xBEEF"])
 def test_ragged_plan_under_asan_ubsan(plan_check, seed):
     """The descriptor / layout / overlap logic of a ragged call is host code
     (ragged_plan.hpp): a stand-alone program drives it over seeded mixes."""
-    import os
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(plan_check), seed], capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "0 failures" in r.stdout
+    assert "0 failures" in B.run_check(plan_check, seed)

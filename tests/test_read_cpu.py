@@ -5,15 +5,13 @@ plain arithmetic, and the host logic behind them
 (carbonado_amd/csrc/read_plan.hpp) as a stand-alone program under ASan +
 UBSan."""
 import ctypes
-import os
 import random
 import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import pytest
 
+import boundary as B
 import test_rust_shim as RS
 from carbonado_amd import _lib
 
@@ -26,61 +24,23 @@ OK, INVALID_ARG, HASH_DECODE, TRUNCATED, NO_DEVICE = 0, 1, 4, 6, 100
 
 
 def read_prototypes() -> dict:
-    text = RS._strip_comments(READ_HEADER.read_text())
-    protos = {}
-    for ret, name, params in re.findall(r"CHIPD_API\s+([^;{}()]*?)\b(chipd_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
-        ps = []
-        params = " ".join(params.split())
-        if params and params != "void":
-            for p in params.split(","):
-                m = re.match(r"(.*?)(\w+)$", p.strip())
-                ps.append((m.group(2), RS.c_to_rust(m.group(1))))
-        protos[name] = (RS.c_to_rust(ret), ps)
-    return protos
-
-
-def _exported() -> set:
-    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    return {line.split()[-1] for line in out.splitlines() if " T " in line}
+    return B.prototypes(READ_HEADER, "chipd_")
 
 
 def test_read_exports_header_and_ctypes_are_one_set():
     protos = read_prototypes()
     assert len(protos) == 4
-    exported = _exported()
-    assert set(protos) == {s for s in exported if s.startswith("chipd_")} == set(_lib.READ_SIGNATURES)
-    for name, (_, ps) in protos.items():
-        assert len(_lib.READ_SIGNATURES[name][1]) == len(ps), name
+    exported = B.exported()
+    B.assert_one_set(protos, exported, "chipd_")
     assert _lib.lib().chipd_abi_version() == 1
     assert "#define CHIPD_ABI_VERSION 1" in READ_HEADER.read_text()
     # the four older boundaries keep their sets
-    assert len({s for s in exported if s.startswith("chip_")}) == 62
-    assert len({s for s in exported if s.startswith("chipx_")}) == 5
-    assert len({s for s in exported if s.startswith("chipa_")}) == 6
-    assert len({s for s in exported if s.startswith("chipr_")}) == 4
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.AUDIT_SIGNATURES) |
-              set(_lib.REPAIR_SIGNATURES))
-    assert not set(_lib.READ_SIGNATURES) & others
+    B.assert_older_keep_their_sets(exported, "chipd_")
 
 
 def test_ffi_read_declares_every_prototype_with_matching_types():
-    text = RS._strip_comments(FFI_READ.read_text())
-    decls = {}
-    for block in re.findall(r'extern\s+"C"\s*\{(.*?)\n\}', text, flags=re.S):
-        for name, params, ret in re.findall(r"pub\s+fn\s+(chipd_\w+)\s*\(([^)]*)\)\s*(?:->\s*([^;]+?))?\s*;", block,
-                                            flags=re.S):
-            assert name not in decls
-            ps = [tuple(" ".join(s.split()) for s in p.split(":", 1))
-                  for p in filter(None, (x.strip() for x in " ".join(params.split()).split(",")))]
-            decls[name] = (" ".join(ret.split()) if ret else "", ps)
-    protos = read_prototypes()
-    assert set(decls) == set(protos)
-    for name, (cret, cps) in protos.items():
-        rret, rps = decls[name]
-        assert cret == rret, name
-        assert [t for _, t in cps] == [t for _, t in rps], name
-        assert [n for n, _ in cps] == [n for n, _ in rps], name
+    B.assert_ffi_matches(B.ffi_declarations(FFI_READ, "chipd_"), read_prototypes())
+    text = B.ffi_text(FFI_READ)
     assert re.search(r"pub const CHIPD_ABI_VERSION: c_int = 1;", text)
 
 
@@ -240,14 +200,7 @@ def test_read_layout_matches_plain_arithmetic():
 
 @pytest.fixture(scope="module")
 def plan_check(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("read_asan") / "read_plan_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", str(ROOT / "tests" / "read_plan_check.cpp"), "-I" + str(ROOT / "include"),
-           "-o", str(exe)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
-    return exe
+    return B.build_check(tmp_path_factory, "read_plan_check.cpp")
 
 
 @pytest.mark.parametrize("seed", ["1", "0xBEEF"])
@@ -259,8 +212,4 @@ def test_read_plan_under_asan_ubsan(plan_check, seed):
     scratch regions disjoint inside the reported length) and multiplies
     the mask table's coefficients with the selected rows of the encoding matrix
     for all 163 masks of four or more shares."""
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(plan_check), seed], capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "0 failures" in r.stdout
+    assert "0 failures" in B.run_check(plan_check, seed)

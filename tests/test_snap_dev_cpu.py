@@ -7,9 +7,7 @@ snap_plan.hpp) as a stand-alone program under ASan + UBSan against
 host_snap.cpp."""
 import ctypes
 import json
-import os
 import re
-import shutil
 import subprocess
 import sys
 from pathlib import Path
@@ -17,6 +15,7 @@ from pathlib import Path
 import pytest
 
 import test_read_cpu as RC
+import boundary as B
 import test_rust_shim as RS
 from carbonado_amd import _lib
 
@@ -33,36 +32,18 @@ SNAP_FORMATS = (6, 7, 10, 11, 14, 15)
 
 
 def prototypes() -> dict:
-    text = RS._strip_comments(HEADER.read_text())
-    protos = {}
-    for ret, name, params in re.findall(r"CHIPS_API\s+([^;{}()]*?)\b(chips_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
-        ps = []
-        params = " ".join(params.split())
-        if params and params != "void":
-            for p in params.split(","):
-                m = re.match(r"(.*?)(\w+)$", p.strip())
-                ps.append((m.group(2), RS.c_to_rust(m.group(1))))
-        protos[name] = (RS.c_to_rust(ret), ps)
-    return protos
+    return B.prototypes(HEADER, "chips_")
 
 
 def test_exports_header_and_ctypes_are_one_set():
     protos = prototypes()
     assert set(protos) == NAMES and len(NAMES) == 10
-    exported = RC._exported()
-    assert set(protos) == {s for s in exported if s.startswith("chips_")} == set(_lib.SNAP_SIGNATURES)
-    for name, (_, ps) in protos.items():
-        assert len(_lib.SNAP_SIGNATURES[name][1]) == len(ps), name
+    exported = B.exported()
+    B.assert_one_set(protos, exported, "chips_")
     assert _lib.lib().chips_abi_version() == 1
     assert "#define CHIPS_ABI_VERSION 1" in HEADER.read_text()
     # the seven older boundaries keep their sets ("chips_" does not start with "chip_")
-    for prefix, n in (("chip_", 62), ("chipx_", 5), ("chipa_", 6), ("chipr_", 4), ("chipd_", 4), ("chipv_", 3),
-                      ("chipe_", 10)):
-        assert len({s for s in exported if s.startswith(prefix)}) == n, prefix
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.AUDIT_SIGNATURES) |
-              set(_lib.REPAIR_SIGNATURES) | set(_lib.READ_SIGNATURES) | set(_lib.VREAD_SIGNATURES) |
-              set(_lib.ECIES_SIGNATURES))
-    assert not set(_lib.SNAP_SIGNATURES) & others
+    B.assert_older_keep_their_sets(exported, "chips_")
     # the argument lists the issue fixes
     assert [n for n, _ in protos["chips_snap_ragged_dev"][1]] == [
         "d_in", "in_off", "n", "count", "d_out", "out_off", "d_out_len", "d_scratch", "scratch_len", "stream"]
@@ -97,22 +78,8 @@ def test_older_entry_points_still_refuse_the_snappy_bit():
 
 
 def test_ffi_snap_declares_every_prototype_with_matching_types():
-    text = RS._strip_comments(FFI.read_text())
-    decls = {}
-    for block in re.findall(r'extern\s+"C"\s*\{(.*?)\n\}', text, flags=re.S):
-        for name, params, ret in re.findall(r"pub\s+fn\s+(chips_\w+)\s*\(([^)]*)\)\s*(?:->\s*([^;]+?))?\s*;", block,
-                                            flags=re.S):
-            assert name not in decls
-            ps = [tuple(" ".join(s.split()) for s in p.split(":", 1))
-                  for p in filter(None, (x.strip() for x in " ".join(params.split()).split(",")))]
-            decls[name] = (" ".join(ret.split()) if ret else "", ps)
-    protos = prototypes()
-    assert set(decls) == set(protos)
-    for name, (cret, cps) in protos.items():
-        rret, rps = decls[name]
-        assert cret == rret, name
-        assert [t for _, t in cps] == [t for _, t in rps], name
-        assert [n for n, _ in cps] == [n for n, _ in rps], name
+    B.assert_ffi_matches(B.ffi_declarations(FFI, "chips_"), prototypes())
+    text = B.ffi_text(FFI)
     assert re.search(r"pub const CHIPS_ABI_VERSION: c_int = 1;", text)
 
 
@@ -330,14 +297,8 @@ def test_scratch_and_layout_lengths():
 
 @pytest.fixture(scope="module")
 def snap_check(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("snap_asan") / "snap_device_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", str(ROOT / "tests" / "snap_device_check.cpp"),
-           str(ROOT / "carbonado_amd" / "csrc" / "host_snap.cpp"), "-I" + str(ROOT / "include"), "-o", str(exe)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
-    return exe
+    return B.build_check(tmp_path_factory, "snap_device_check.cpp",
+                         extra_sources=[ROOT / "carbonado_amd" / "csrc" / "host_snap.cpp"])
 
 
 @pytest.mark.parametrize("args", [["1"], ["0xBEEF"], ["3", "big"]])
@@ -347,11 +308,7 @@ def test_snap_device_and_plan_under_asan_ubsan(snap_check, args):
     compressed as the kernels split them against host::snap_compress byte for
     byte, the block decoder against host::decompress_raw on good and corrupt
     bodies, and the plan."""
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(snap_check)] + args, capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "0 failures" in r.stdout
+    assert "0 failures" in B.run_check(snap_check, *args, timeout=300)
 
 
 def test_snap_bench_dry_run():

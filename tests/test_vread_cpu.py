@@ -4,15 +4,14 @@ read decides before it touches a device, in their stated order, the scratch
 length, and the host logic behind them (carbonado_amd/csrc/vread_plan.hpp) as
 a stand-alone program under ASan + UBSan."""
 import ctypes
-import os
 import re
-import shutil
 import subprocess
 from pathlib import Path
 
 import pytest
 
 import test_read_cpu as RC
+import boundary as B
 import test_rust_shim as RS
 from carbonado_amd import _lib
 
@@ -26,26 +25,14 @@ STRICT = 1
 
 
 def vread_prototypes() -> dict:
-    text = RS._strip_comments(VREAD_HEADER.read_text())
-    protos = {}
-    for ret, name, params in re.findall(r"CHIPV_API\s+([^;{}()]*?)\b(chipv_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.S):
-        ps = []
-        params = " ".join(params.split())
-        if params and params != "void":
-            for p in params.split(","):
-                m = re.match(r"(.*?)(\w+)$", p.strip())
-                ps.append((m.group(2), RS.c_to_rust(m.group(1))))
-        protos[name] = (RS.c_to_rust(ret), ps)
-    return protos
+    return B.prototypes(VREAD_HEADER, "chipv_")
 
 
 def test_vread_exports_header_and_ctypes_are_one_set():
     protos = vread_prototypes()
     assert set(protos) == {"chipv_abi_version", "chipv_read_scratch_len", "chipv_read_ranges_dev"}
-    exported = RC._exported()
-    assert set(protos) == {s for s in exported if s.startswith("chipv_")} == set(_lib.VREAD_SIGNATURES)
-    for name, (_, ps) in protos.items():
-        assert len(_lib.VREAD_SIGNATURES[name][1]) == len(ps), name
+    exported = B.exported()
+    B.assert_one_set(protos, exported, "chipv_")
     assert _lib.lib().chipv_abi_version() == 1
     text = VREAD_HEADER.read_text()
     assert "#define CHIPV_ABI_VERSION 1" in text and "#define CHIPV_STRICT 1u" in text
@@ -56,36 +43,15 @@ def test_vread_exports_header_and_ctypes_are_one_set():
     types = dict(protos["chipv_read_ranges_dev"][1])
     assert types["d_vouch"] == "*mut u32" and types["flags"] == "u32"
     # the five older boundaries keep their sets
-    assert len({s for s in exported if s.startswith("chip_")}) == 62
-    assert len({s for s in exported if s.startswith("chipx_")}) == 5
-    assert len({s for s in exported if s.startswith("chipa_")}) == 6
-    assert len({s for s in exported if s.startswith("chipr_")}) == 4
-    assert len({s for s in exported if s.startswith("chipd_")}) == 4
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.AUDIT_SIGNATURES) |
-              set(_lib.REPAIR_SIGNATURES) | set(_lib.READ_SIGNATURES))
-    assert not set(_lib.VREAD_SIGNATURES) & others
+    B.assert_older_keep_their_sets(exported, "chipv_")
     # the ctypes of the new call: those of the old one with the two arguments put in
     o, n = _lib.READ_SIGNATURES["chipd_read_ranges_dev"][1], _lib.VREAD_SIGNATURES["chipv_read_ranges_dev"][1]
     assert n == o[:16] + [ctypes.c_void_p, ctypes.c_uint32] + o[16:]
 
 
 def test_ffi_vread_declares_every_prototype_with_matching_types():
-    text = RS._strip_comments(FFI_VREAD.read_text())
-    decls = {}
-    for block in re.findall(r'extern\s+"C"\s*\{(.*?)\n\}', text, flags=re.S):
-        for name, params, ret in re.findall(r"pub\s+fn\s+(chipv_\w+)\s*\(([^)]*)\)\s*(?:->\s*([^;]+?))?\s*;", block,
-                                            flags=re.S):
-            assert name not in decls
-            ps = [tuple(" ".join(s.split()) for s in p.split(":", 1))
-                  for p in filter(None, (x.strip() for x in " ".join(params.split()).split(",")))]
-            decls[name] = (" ".join(ret.split()) if ret else "", ps)
-    protos = vread_prototypes()
-    assert set(decls) == set(protos)
-    for name, (cret, cps) in protos.items():
-        rret, rps = decls[name]
-        assert cret == rret, name
-        assert [t for _, t in cps] == [t for _, t in rps], name
-        assert [n for n, _ in cps] == [n for n, _ in rps], name
+    B.assert_ffi_matches(B.ffi_declarations(FFI_VREAD, "chipv_"), vread_prototypes())
+    text = B.ffi_text(FFI_VREAD)
     assert re.search(r"pub const CHIPV_ABI_VERSION: c_int = 1;", text)
     header = VREAD_HEADER.read_text()
     for name in ("CHIPV_VOUCHED", "CHIPV_UNVOUCHED", "CHIPV_CONTRADICTED", "CHIPV_STRICT"):
@@ -200,14 +166,7 @@ def test_vread_scratch_length():
 
 @pytest.fixture(scope="module")
 def plan_check(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = tmp_path_factory.mktemp("vread_asan") / "vread_plan_check"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", str(ROOT / "tests" / "vread_plan_check.cpp"), "-I" + str(ROOT / "include"),
-           "-o", str(exe)]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
-    return exe
+    return B.build_check(tmp_path_factory, "vread_plan_check.cpp")
 
 
 @pytest.mark.parametrize("seed", ["1", "0xBEEF"])
@@ -217,11 +176,7 @@ def test_vread_plan_under_asan_ubsan(plan_check, seed):
     seeded mixes (the plan is a ranged read's plan, the scratch regions are
     disjoint inside the reported length, the vouch items of a segment are its
     window's chunks and every item maps back to (segment, chunk) once)."""
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(plan_check), seed], capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "0 failures" in r.stdout
+    assert "0 failures" in B.run_check(plan_check, seed)
 
 
 def test_vread_bench_dry_run():

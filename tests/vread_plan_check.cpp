@@ -121,7 +121,7 @@ int main(int argc, char **argv) {
         for (uint64_t i = 0; i < p.vouch_items; i += stride) items.push_back(i);
         if (!items.empty() && items.back() + 1 != p.vouch_items) items.push_back(p.vouch_items - 1);
         for (const uint64_t i : items) {
-            const uint32_t g = vread::item_segment(pre, (uint32_t)ns, i);
+            const uint32_t g = audit::prefix_find(pre, (uint32_t)ns, i);
             EXPECT(g < ns && pre[g] <= i && i < pre[g + 1]);
             const read::Seg &sg = p.rd.segs()[g];
             const audit::Req &a = p.rd.ka.reqs()[g];
