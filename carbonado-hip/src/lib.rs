@@ -29,6 +29,7 @@ mod ffi_vread;
 mod ffi_ecies;
 mod ffi_snap;
 mod ffi_cread;
+mod ffi_fread;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -1776,6 +1777,210 @@ pub fn read_plain_ranges(keys: &[u8], ivs: &[u8], key_status: Option<&[u32]>, in
                                          content_off.as_ptr(), clen.as_mut_ptr(), status.as_mut_ptr() as *mut u32,
                                          used.as_mut_ptr() as *mut u32, vouch.as_mut_ptr() as *mut u32, flags,
                                          scratch.ptr, scratch.len() as u64, stream.0)
+    })?;
+    Ok(clen)
+}
+
+fn abi_fread() -> Result<()> {
+    abi_cread()?;
+    match unsafe { ffi_fread::chipf_abi_version() } {
+        ffi_fread::CHIPF_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// The frame index of resident level-14 / level-15 streams: `nframes[s] + 1`
+/// ascending offsets into stream s's frame stream from entry `idx_off[s]` of
+/// `frame_off`, the last one its length; with what proved it.
+#[derive(Debug, Clone, Default)]
+pub struct FrameIndex {
+    pub frame_off: Vec<u64>,
+    pub idx_off: Vec<u64>,
+    pub nframes: Vec<u64>,
+    /// 0 for a proven index; 2 for a capacity below `nframes + 1`; 11 for a valid
+    /// stream that is not canonical; 5, 7 or 16 (with a vouch bit where a header's
+    /// primary copy is damaged: scrub, then build again); the stream's key status.
+    pub index_status: Vec<u32>,
+    pub plain_len: Vec<u64>,
+    pub index_vouch: Vec<u32>,
+}
+
+fn key_ptrs(format: u8, keys: Option<(&[u8], &[u8])>, key_status: Option<&[u32]>, count: usize)
+            -> Result<(*const u8, *const u8, *const u32)> {
+    match (format, keys) {
+        (15, Some((k, v))) if k.len() == 32 * count && v.len() == 16 * count &&
+            key_status.map_or(true, |s| s.len() == count) =>
+            Ok((k.as_ptr(), v.as_ptr(), key_status.map_or(ptr::null(), |s| s.as_ptr()))),
+        (14, _) => Ok((ptr::null(), ptr::null(), ptr::null())),
+        _ => Err(ChipError::InvalidArgument),
+    }
+}
+
+/// Scratch of a [`frame_index`] or [`verify_frame_index`] call over `nstreams`
+/// streams and `nentries` index entries in all.
+pub fn frame_index_scratch(nstreams: u64, nentries: u64) -> u64 {
+    unsafe { ffi_fread::chipf_index_scratch_len(nstreams, nentries) }
+}
+
+/// Builds and proves the frame index of every resident level-14 / level-15
+/// stream (`keys`: the AES keys and nonces of [`stream_keys`], for format 15):
+/// a serial walk over the chunk headers of the primary copy, then
+/// [`verify_frame_index`]'s work over what it found.  Stream s may write
+/// `idx_cap[s]` entries from entry `idx_off[s]`.  The call waits twice.
+#[allow(clippy::too_many_arguments)]
+pub fn frame_index(format: u8, keys: Option<(&[u8], &[u8])>, key_status: Option<&[u32]>, input: &DeviceBuffer,
+                   in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer, padding: &[u32], chunk_len: &[u32],
+                   idx_off: &[u64], idx_cap: &[u64], scratch: &mut DeviceBuffer, stream: Stream)
+                   -> Result<FrameIndex> {
+    let count = in_len.len();
+    if in_off.len() != count || padding.len() != count || chunk_len.len() != count || idx_off.len() != count ||
+        idx_cap.len() != count || hashes.len() < count * HASH_LEN || !ranges_fit(in_off, in_len, 0, input.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (pk, pv, pks) = key_ptrs(format, keys, key_status, count)?;
+    abi_fread()?;
+    let total = idx_off.iter().zip(idx_cap).map(|(o, c)| o.saturating_add(*c)).max().unwrap_or(0);
+    let mut ix = FrameIndex {
+        frame_off: vec![0u64; total as usize],
+        idx_off: idx_off.to_vec(),
+        nframes: vec![0u64; count],
+        index_status: vec![0u32; count],
+        plain_len: vec![0u64; count],
+        index_vouch: vec![0u32; count],
+    };
+    check(unsafe {
+        ffi_fread::chipf_frame_index_dev(format, pk, pv, pks, input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(),
+                                         hashes.as_ptr(), padding.as_ptr(), chunk_len.as_ptr(), count as u64,
+                                         ix.frame_off.as_mut_ptr(), idx_off.as_ptr(), idx_cap.as_ptr(),
+                                         ix.nframes.as_mut_ptr(), ix.index_status.as_mut_ptr(),
+                                         ix.plain_len.as_mut_ptr(), ix.index_vouch.as_mut_ptr(), scratch.ptr,
+                                         scratch.len() as u64, stream.0)
+    })?;
+    Ok(ix)
+}
+
+/// Proves `index` against the streams: a strict vouched read of the identifier
+/// and of every chunk header, the keystream over them at 15, the chain check.
+/// `index_status` (u32), `plain_len` (u64) and `index_vouch` (u32), one entry
+/// per stream on the device.  Enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn verify_frame_index(format: u8, keys: Option<(&[u8], &[u8])>, key_status: Option<&[u32]>, input: &DeviceBuffer,
+                          in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer, padding: &[u32], chunk_len: &[u32],
+                          index: &FrameIndex, index_status: &mut DeviceBuffer, plain_len: &mut DeviceBuffer,
+                          index_vouch: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    let count = in_len.len();
+    if in_off.len() != count || padding.len() != count || chunk_len.len() != count || !index_holds(index, count) ||
+        hashes.len() < count * HASH_LEN || index_status.len() < 4 * count || plain_len.len() < 8 * count ||
+        index_vouch.len() < 4 * count || !ranges_fit(in_off, in_len, 0, input.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (pk, pv, pks) = key_ptrs(format, keys, key_status, count)?;
+    abi_fread()?;
+    check(unsafe {
+        ffi_fread::chipf_verify_index_dev(format, pk, pv, pks, input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(),
+                                          hashes.as_ptr(), padding.as_ptr(), chunk_len.as_ptr(), count as u64,
+                                          index.frame_off.as_ptr(), index.idx_off.as_ptr(), index.nframes.as_ptr(),
+                                          index_status.as_mut_ptr() as *mut u32, plain_len.as_mut_ptr() as *mut u64,
+                                          index_vouch.as_mut_ptr() as *mut u32, scratch.ptr, scratch.len() as u64,
+                                          stream.0)
+    })
+}
+
+// every stream's entries lie inside the index's offsets
+fn index_holds(index: &FrameIndex, count: usize) -> bool {
+    index.idx_off.len() == count && index.nframes.len() == count && index.plain_len.len() == count &&
+        index.idx_off.iter().zip(&index.nframes).all(|(o, n)| {
+            o.checked_add(*n).and_then(|e| e.checked_add(1)).map_or(false, |e| e <= index.frame_off.len() as u64)
+        })
+}
+
+/// What [`read_frame_ranges`] needs of the requests: content offsets and lengths
+/// of plaintext `[start, min(plain_len, start + len))`, their total, the number
+/// of (request, frame) work items, the bytes of the staging rows and the
+/// segments of the vouched read.
+#[derive(Debug, Clone, Default)]
+pub struct FrameReadLayout {
+    pub content_off: Vec<u64>,
+    pub content_len: Vec<u64>,
+    pub content_total: u64,
+    pub nseg: u64,
+    pub stage_total: u64,
+    pub vseg: u64,
+}
+
+/// Host only: the layout of the requests over `index` (with its `index_status`
+/// as the read takes it).
+#[allow(clippy::too_many_arguments)]
+pub fn frame_read_layout(format: u8, chunk_len: &[u32], padding: &[u32], index: &FrameIndex, use_status: bool,
+                         req_stream: &[u32], start: &[u64], len: &[u64], align: u64) -> Result<FrameReadLayout> {
+    let (count, nreq) = (chunk_len.len(), req_stream.len());
+    if padding.len() != count || !index_holds(index, count) || start.len() != nreq || len.len() != nreq ||
+        (use_status && index.index_status.len() != count) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let mut l = FrameReadLayout { content_off: vec![0u64; nreq], content_len: vec![0u64; nreq], ..Default::default() };
+    check(unsafe {
+        ffi_fread::chipf_read_layout(format, chunk_len.as_ptr(), padding.as_ptr(),
+                                     if use_status { index.index_status.as_ptr() } else { ptr::null() },
+                                     index.frame_off.as_ptr(), index.idx_off.as_ptr(), index.nframes.as_ptr(),
+                                     index.plain_len.as_ptr(), count as u64, req_stream.as_ptr(), start.as_ptr(),
+                                     len.as_ptr(), nreq as u64, align, l.content_off.as_mut_ptr(),
+                                     l.content_len.as_mut_ptr(), &mut l.content_total, &mut l.nseg,
+                                     &mut l.stage_total, &mut l.vseg)
+    })?;
+    Ok(l)
+}
+
+/// Scratch of a [`read_frame_ranges`] call (the numbers of [`frame_read_layout`]).
+pub fn frame_read_scratch(layout: &FrameReadLayout, nstreams: u64) -> u64 {
+    unsafe {
+        ffi_fread::chipf_read_scratch_len(layout.content_off.len() as u64, layout.nseg, layout.stage_total, layout.vseg,
+                                          nstreams)
+    }
+}
+
+/// Plaintext bytes `[start[r], start[r] + len[r])` of resident level-14 /
+/// level-15 stream `req_stream[r]` into `content[content_off[r]..]` (any byte
+/// offset), with an index that [`frame_index`] or [`verify_frame_index`]
+/// proved: [`read_ranges_vouched`] of the compressed frames behind the range,
+/// the keystream taken off them at 15, one block decode per frame with header
+/// and CRC checked, only the wanted bytes stored.  Status per request: 0, the
+/// read's 5 or 7, 16 for a frame that disagrees with the index or its CRC (a
+/// wrong key at 15 among them), or the stream's index status where `use_status`
+/// and that is not zero; content is the exact plaintext for 0, zeros otherwise.
+/// The GCM tag is NOT checked.  Enqueued on `stream`, not synchronised.  Returns
+/// the content length per request.
+#[allow(clippy::too_many_arguments)]
+pub fn read_frame_ranges(format: u8, keys: Option<(&[u8], &[u8])>, index: &FrameIndex, use_status: bool,
+                         input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer, padding: &[u32],
+                         chunk_len: &[u32], req_stream: &[u32], start: &[u64], len: &[u64],
+                         content: &mut DeviceBuffer, content_off: &[u64], status: &mut DeviceBuffer,
+                         used: &mut DeviceBuffer, vouch: &mut DeviceBuffer, flags: u32, scratch: &mut DeviceBuffer,
+                         stream: Stream) -> Result<Vec<u64>> {
+    let (count, nreq) = (in_len.len(), req_stream.len());
+    if in_off.len() != count || padding.len() != count || chunk_len.len() != count || content_off.len() != nreq ||
+        hashes.len() < count * HASH_LEN || status.len() < nreq * 4 || used.len() < nreq * 4 || vouch.len() < nreq * 4 ||
+        !ranges_fit(in_off, in_len, 0, input.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let want = frame_read_layout(format, chunk_len, padding, index, use_status, req_stream, start, len, 16)?;
+    if !ranges_fit(content_off, &want.content_len, 0, content.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (pk, pv, _) = key_ptrs(format, keys, None, count)?;
+    abi_fread()?;
+    let mut clen = vec![0u64; nreq];
+    check(unsafe {
+        ffi_fread::chipf_read_ranges_dev(format, pk, pv,
+                                         if use_status { index.index_status.as_ptr() } else { ptr::null() },
+                                         index.frame_off.as_ptr(), index.idx_off.as_ptr(), index.nframes.as_ptr(),
+                                         index.plain_len.as_ptr(), input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(),
+                                         hashes.as_ptr(), padding.as_ptr(), chunk_len.as_ptr(), count as u64,
+                                         req_stream.as_ptr(), start.as_ptr(), len.as_ptr(), nreq as u64,
+                                         content.as_mut_ptr(), content_off.as_ptr(), clen.as_mut_ptr(),
+                                         status.as_mut_ptr() as *mut u32, used.as_mut_ptr() as *mut u32,
+                                         vouch.as_mut_ptr() as *mut u32, flags, scratch.ptr, scratch.len() as u64,
+                                         stream.0)
     })?;
     Ok(clen)
 }

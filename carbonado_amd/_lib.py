@@ -332,6 +332,32 @@ CREAD_SIGNATURES = {
                                              ctypes.c_void_p]),
 }
 
+# the fread header (include/carbonado_hip_fread.h): plaintext ranged reads of
+# level-14 and level-15 streams (the index check, the index build, the read),
+# a tenth table of its own
+FREAD_SIGNATURES = {
+    "chipf_abi_version": (ctypes.c_int, []),
+    "chipf_index_scratch_len": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "chipf_verify_index_dev": (ctypes.c_int, [ctypes.c_uint8, c_u8p, c_u8p, c_u32p, ctypes.c_void_p, c_u64p, c_u64p,
+                                              ctypes.c_void_p, c_u32p, c_u32p, ctypes.c_uint64, c_u64p, c_u64p, c_u64p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_uint64, ctypes.c_void_p]),
+    "chipf_frame_index_dev": (ctypes.c_int, [ctypes.c_uint8, c_u8p, c_u8p, c_u32p, ctypes.c_void_p, c_u64p, c_u64p,
+                                             ctypes.c_void_p, c_u32p, c_u32p, ctypes.c_uint64, c_u64p, c_u64p, c_u64p,
+                                             c_u64p, c_u32p, c_u64p, c_u32p, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.c_void_p]),
+    "chipf_read_layout": (ctypes.c_int, [ctypes.c_uint8, c_u32p, c_u32p, c_u32p, c_u64p, c_u64p, c_u64p, c_u64p,
+                                         ctypes.c_uint64, c_u32p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_uint64,
+                                         c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, c_u64p]),
+    "chipf_read_scratch_len": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                 ctypes.c_uint64]),
+    "chipf_read_ranges_dev": (ctypes.c_int, [ctypes.c_uint8, c_u8p, c_u8p, c_u32p, c_u64p, c_u64p, c_u64p, c_u64p,
+                                             ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p, c_u32p, c_u32p,
+                                             ctypes.c_uint64, c_u32p, c_u64p, c_u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                             c_u64p, c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -354,7 +380,7 @@ def lib() -> ctypes.CDLL:
         l = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES,
                                   **READ_SIGNATURES, **VREAD_SIGNATURES, **ECIES_SIGNATURES,
-                                  **SNAP_SIGNATURES, **CREAD_SIGNATURES}.items():
+                                  **SNAP_SIGNATURES, **CREAD_SIGNATURES, **FREAD_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

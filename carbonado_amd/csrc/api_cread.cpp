@@ -4,18 +4,17 @@
 // that a host function wipes behind the upload), enqueues the kernels of
 // cread_kernels.hip and, last, the memset that zeroes the key region.  The
 // stream keys and the read run the vouched read of api_vread.cpp in front.
-#include "api_common.hpp"
+#include "api_cread.hpp"
 #include "api_vread.hpp"
 #include "cread_kernels.hpp"
-#include "cread_plan.hpp"
 #include "key_upload.hpp"
 
 using namespace chip;
 using namespace chip::api;
 
-namespace {
+namespace chip {
+namespace api {
 
-// the table, the two launches and the memset of a planned keystream call
 int ctr_enqueue(cread::Plan &p, uint8_t *d_buf, const uint32_t *d_gate, uint32_t *d_status, uint32_t *d_used,
                 uint32_t *d_vouch, void *d_scratch, void *stream) {
     if (p.work == 0) {  // nothing has bytes: no key is used and none is uploaded
@@ -45,6 +44,11 @@ int ctr_enqueue(cread::Plan &p, uint8_t *d_buf, const uint32_t *d_gate, uint32_t
     CHIP_HIP(w);
     return CHIP_OK;
 }
+
+}  // namespace api
+}  // namespace chip
+
+namespace {
 
 // f(o) for every stream on the stage pool's threads and the caller
 void for_streams(uint64_t count, const std::function<void(uint64_t)> &f) {

@@ -1119,6 +1119,182 @@ def decode_ragged_snap(fmt: int, enc: torch.Tensor, in_off, in_len, hashes: torc
                                              _p(out_len), _p(status), _p(scratch), _stream()))
 
 
+# ---- plaintext ranged reads of level-14 / level-15 streams
+# (include/carbonado_hip_fread.h): the frame index of resident streams, its
+# proof against the stream, the read
+
+def _stream_args(streams, in_off, in_len, hashes, padding, chunk_len):
+    assert streams.is_cuda and hashes.is_cuda and streams.dtype == torch.uint8
+    assert streams.is_contiguous() and hashes.is_contiguous()
+    ioff, pioff, nstreams = _arr(in_off)
+    ilen, pilen, nl = _arr(in_len)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    cl, pcl, ncl = _arr(chunk_len, np.uint32)
+    assert nl == nstreams == npad == ncl
+    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
+    return (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams
+
+
+def _frame_keys(fmt, keys, ivs, key_status, nstreams):
+    """(keep-alive, keys pointer, ivs pointer, key_status pointer): looked at for format 15 only"""
+    if fmt != 15 or keys is None:
+        return None, None, None, None
+    kk, pk, vv, pv = _gcm_keys(keys, ivs, nstreams)
+    ks, pks = None, None
+    if key_status is not None:
+        ks, pks, nks = _arr(key_status, np.uint32)
+        assert nks == nstreams
+    return (kk, vv, ks), pk, pv, pks
+
+
+def frame_index_scratch(nstreams: int, nentries: int, device=None) -> torch.Tensor:
+    """Scratch of a frame_index or verify_frame_index call over nstreams streams
+    and nentries index entries in all (the capacities, or nframes + 1 each)."""
+    size = _lib.lib().chipf_index_scratch_len(nstreams, nentries)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def frame_index(fmt: int, streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len, idx_off,
+                idx_cap, scratch: torch.Tensor, keys=None, ivs=None, key_status=None):
+    """The frame index of every resident level-14 / level-15 stream, built by a
+    serial walk over the chunk headers of the primary copy (decrypted hop by hop
+    at 15, with keys, ivs and key_status as stream_keys gave them) and proven by
+    verify_frame_index's work.  Stream s may write idx_cap[s] entries from entry
+    idx_off[s] of one offsets array.  The call waits twice.  Returns numpy
+    arrays (frame_off, nframes, index_status, plain_len, index_vouch):
+    index_status 0 for a proven index of nframes + 1 entries; 2 where idx_cap
+    is below nframes + 1; 11 for a valid stream that is not canonical; 16, 5 or
+    7 with a vouch bit for a stream whose header's primary copy is damaged
+    (scrub_ragged, then call again)."""
+    (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
+                                                                              chunk_len)
+    io, pio, nio = _arr(idx_off)
+    cap, pcap, ncap = _arr(idx_cap)
+    assert nio == nstreams == ncap and scratch.is_cuda
+    total = int((io[:nstreams] + cap[:nstreams]).max()) if nstreams else 0
+    frame_off = np.zeros(max(total, 1), dtype=np.uint64)
+    nframes = np.zeros(max(nstreams, 1), dtype=np.uint64)
+    status = np.zeros(max(nstreams, 1), dtype=np.uint32)
+    plain = np.zeros(max(nstreams, 1), dtype=np.uint64)
+    vouch = np.zeros(max(nstreams, 1), dtype=np.uint32)
+    keep, pk, pv, pks = _frame_keys(fmt, keys, ivs, key_status, nstreams)
+    check(_lib.lib().chipf_frame_index_dev(fmt, pk, pv, pks, _p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams,
+                                           frame_off.ctypes.data_as(_lib.c_u64p), pio, pcap,
+                                           nframes.ctypes.data_as(_lib.c_u64p), status.ctypes.data_as(_lib.c_u32p),
+                                           plain.ctypes.data_as(_lib.c_u64p), vouch.ctypes.data_as(_lib.c_u32p),
+                                           _p(scratch), scratch.numel(), _stream()))
+    return frame_off[:total], nframes[:nstreams], status[:nstreams], plain[:nstreams], vouch[:nstreams]
+
+
+def verify_frame_index(fmt: int, streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len,
+                       frame_off, idx_off, nframes, index_status: torch.Tensor, plain_len: torch.Tensor,
+                       index_vouch: torch.Tensor, scratch: torch.Tensor, keys=None, ivs=None, key_status=None) -> None:
+    """Proves the index frame_off[idx_off[s] : idx_off[s] + nframes[s] + 1] of
+    every stream against the stream: a strict vouched read of the identifier and
+    of every chunk header, the keystream over them at 15, the chain check.
+    index_status (int32 / uint32), plain_len (int64) and index_vouch (int32 /
+    uint32), one entry per stream on the device: 0 and the plaintext's length
+    for an index whose every link holds; the read's 5 or 7; 16 for a wrong
+    link; 11 for a chain that is not canonical.  Enqueued on the current stream,
+    not synchronised."""
+    (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
+                                                                              chunk_len)
+    fo, pfo, nfo = _arr(frame_off)
+    io, pio, nio = _arr(idx_off)
+    nf, pnf, nnf = _arr(nframes)
+    assert nio == nstreams == nnf and scratch.is_cuda
+    assert all(int(io[s]) + int(nf[s]) + 1 <= nfo for s in range(nstreams))
+    for t, size in ((index_status, 4), (plain_len, 8), (index_vouch, 4)):
+        assert t.is_cuda and t.numel() >= nstreams and t.element_size() == size and t.is_contiguous()
+    keep, pk, pv, pks = _frame_keys(fmt, keys, ivs, key_status, nstreams)
+    check(_lib.lib().chipf_verify_index_dev(fmt, pk, pv, pks, _p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams,
+                                            pfo, pio, pnf, _p(index_status), _p(plain_len), _p(index_vouch),
+                                            _p(scratch), scratch.numel(), _stream()))
+
+
+def frame_read_layout(fmt: int, chunk_len, padding, frame_off, idx_off, nframes, plain_len, req_stream, start, length,
+                      align: int = 16, index_status=None):
+    """Where read_frame_ranges puts plaintext [start, min(plain_len, start +
+    length)) of every request and what its scratch depends on (host only):
+    (content_off, content_len, content_total, nseg, stage_total, vseg).
+    index_status: as read_frame_ranges takes it."""
+    cl, pcl, nstreams = _arr(chunk_len, np.uint32)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    fo, pfo, nfo = _arr(frame_off)
+    io, pio, nio = _arr(idx_off)
+    nf, pnf, nnf = _arr(nframes)
+    pl, ppl, npl = _arr(plain_len)
+    rs, prs, nreq = _arr(req_stream, np.uint32)
+    st, pst, ns = _arr(start)
+    ln, pln, nl = _arr(length)
+    assert npad == nstreams == nio == nnf == npl and ns == nreq == nl
+    assert all(int(io[s]) + int(nf[s]) + 1 <= nfo for s in range(nstreams))
+    off, clen = np.zeros(max(nreq, 1), dtype=np.uint64), np.zeros(max(nreq, 1), dtype=np.uint64)
+    total, nseg, stage, vseg = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    pis = None
+    if index_status is not None:
+        ist, pis, nis = _arr(index_status, np.uint32)
+        assert nis == nstreams
+    check(_lib.lib().chipf_read_layout(fmt, pcl, ppad, pis, pfo, pio, pnf, ppl, nstreams, prs, pst, pln, nreq, align,
+                                       off.ctypes.data_as(_lib.c_u64p), clen.ctypes.data_as(_lib.c_u64p),
+                                       ctypes.byref(total), ctypes.byref(nseg), ctypes.byref(stage), ctypes.byref(vseg)))
+    return off[:nreq].tolist(), clen[:nreq].tolist(), total.value, nseg.value, stage.value, vseg.value
+
+
+def frame_read_scratch(nreq: int, nseg: int, stage_total: int, vseg: int, nstreams: int, device=None) -> torch.Tensor:
+    """Scratch of a read_frame_ranges call (the numbers of frame_read_layout)."""
+    size = _lib.lib().chipf_read_scratch_len(nreq, nseg, stage_total, vseg, nstreams)
+    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+
+
+def read_frame_ranges(fmt: int, streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len,
+                      frame_off, idx_off, nframes, plain_len, req_stream, start, length, content: torch.Tensor,
+                      content_off, status: torch.Tensor, used: torch.Tensor, vouch: torch.Tensor, scratch: torch.Tensor,
+                      flags: int = 0, keys=None, ivs=None, index_status=None):
+    """Plaintext bytes [start[r], start[r] + length[r]) of level-14 / level-15
+    stream req_stream[r] into content[content_off[r] :] (any byte offset), with
+    an index as frame_index or verify_frame_index proved it: the vouched read of
+    the compressed frames behind the range, the keystream taken off them at 15,
+    one block decode per frame with header and CRC checked, only the wanted
+    bytes stored.  status: 0, the read's 5 or 7, 16 for a frame that does not
+    agree with the index or its CRC (a wrong key at 15 among them), or the
+    stream's index_status where that is non-zero; content is the exact plaintext
+    for 0 and zeros otherwise.  used and vouch as read_ranges_vouched fills
+    them.  The GCM tag is NOT checked.  Enqueued on the current stream, not
+    synchronised.  Returns the content length per request."""
+    (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
+                                                                              chunk_len)
+    assert content.is_cuda and status.is_cuda and used.is_cuda and vouch.is_cuda and scratch.is_cuda
+    assert content.dtype == torch.uint8 and content.dim() == 1 and content.is_contiguous()
+    fo, pfo, nfo = _arr(frame_off)
+    io, pio, nio = _arr(idx_off)
+    nf, pnf, nnf = _arr(nframes)
+    pl, ppl, npl = _arr(plain_len)
+    rs, prs, nreq = _arr(req_stream, np.uint32)
+    st, pst, ns = _arr(start)
+    ln, pln, nln = _arr(length)
+    coff, pcoff, nco = _arr(content_off)
+    assert nio == nstreams == nnf == npl and ns == nreq == nln == nco
+    assert all(int(io[s]) + int(nf[s]) + 1 <= nfo for s in range(nstreams))
+    for t in (status, used, vouch):
+        assert t.numel() >= nreq and t.element_size() == 4 and t.is_contiguous()
+    if nreq and int(rs.max()) < nstreams:  # the content buffer is checked before the call (else: the call reports it)
+        want = np.array([min(max(int(pl[s]) - int(a), 0), int(n)) for s, a, n in zip(rs[:nreq], st[:nreq], ln[:nreq])],
+                        dtype=np.uint64)
+        assert _fits(coff, want, content.numel())
+    keep, pk, pv, _ = _frame_keys(fmt, keys, ivs, None, nstreams)
+    pis = None
+    if index_status is not None:
+        ist, pis, nis = _arr(index_status, np.uint32)
+        assert nis == nstreams
+    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
+    check(_lib.lib().chipf_read_ranges_dev(fmt, pk, pv, pis, pfo, pio, pnf, ppl, _p(streams), pioff, pilen, _p(hashes),
+                                           ppad, pcl, nstreams, prs, pst, pln, nreq, _p(content), pcoff,
+                                           clen.ctypes.data_as(_lib.c_u64p), _p(status), _p(used), _p(vouch), flags,
+                                           _p(scratch), scratch.numel(), _stream()))
+    return clen[:nreq].tolist()
+
+
 def host_topology() -> dict:
     """Where this process's host-copy path sits (chip_host_topology): the
     GPU's NUMA node, the calling thread's staging ring node and the copy
