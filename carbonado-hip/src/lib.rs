@@ -30,6 +30,7 @@ mod ffi_ecies;
 mod ffi_snap;
 mod ffi_cread;
 mod ffi_fread;
+mod ffi_qread;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -1983,6 +1984,112 @@ pub fn read_frame_ranges(format: u8, keys: Option<(&[u8], &[u8])>, index: &Frame
                                          stream.0)
     })?;
     Ok(clen)
+}
+
+fn abi_qread() -> Result<()> {
+    abi_vread()?;
+    match unsafe { ffi_qread::chipq_abi_version() } {
+        ffi_qread::CHIPQ_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// What the planned reads know of a stream table: the number of streams, the
+/// largest chunk count and the smallest non-zero shard length among them.
+pub type TableInfo = ffi_qread::chipq_table_info;
+
+/// Bytes of device memory the table of `nstreams` streams needs ([`stream_table`]).
+pub fn stream_table_len(nstreams: u64) -> u64 {
+    unsafe { ffi_qread::chipq_stream_table_len(nstreams) }
+}
+
+/// Describe resident streams once (the stream arguments of [`read_ranges`])
+/// in `table`, for every later [`read_ranges_planned`] call.  The one upload,
+/// enqueued on `stream`; the table stays valid while the streams and hashes
+/// stay where they are.
+#[allow(clippy::too_many_arguments)]
+pub fn stream_table(input: &DeviceBuffer, in_off: &[u64], in_len: &[u64], hashes: &DeviceBuffer, padding: &[u32],
+                    chunk_len: &[u32], table: &mut DeviceBuffer, stream: Stream) -> Result<TableInfo> {
+    let count = in_len.len();
+    if in_off.len() != count || padding.len() != count || chunk_len.len() != count ||
+        hashes.len() < count * HASH_LEN || (table.len() as u64) < stream_table_len(count as u64) ||
+        !ranges_fit(in_off, in_len, 0, input.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_qread()?;
+    let mut info = TableInfo::default();
+    check(unsafe {
+        ffi_qread::chipq_stream_table_dev(input.as_ptr(), in_off.as_ptr(), in_len.as_ptr(), hashes.as_ptr(),
+                                          padding.as_ptr(), chunk_len.as_ptr(), count as u64, table.ptr,
+                                          table.len() as u64, &mut info, stream.0)
+    })?;
+    Ok(info)
+}
+
+/// Scratch of a [`read_ranges_planned`] (`vouched`: [`read_ranges_vouched_planned`])
+/// call of capacity (`nreq`, `max_len`); 0 where the call would refuse it.
+pub fn planned_read_scratch_len(info: &TableInfo, nreq: u64, max_len: u64, vouched: bool) -> u64 {
+    unsafe { ffi_qread::chipq_read_scratch_len(info, nreq, max_len, vouched as u32) }
+}
+
+fn planned_fits(nreq: u64, max_len: u64, req_stream: &DeviceBuffer, start: &DeviceBuffer, len: &DeviceBuffer,
+                content: &DeviceBuffer, content_stride: u64, content_len: &DeviceBuffer, words: &[&DeviceBuffer])
+                -> bool {
+    let n = nreq as usize;
+    let slot = (max_len + 15) / 16 * 16;
+    req_stream.len() >= n * 4 && start.len() >= n * 8 && len.len() >= n * 8 && content_len.len() >= n * 8 &&
+        words.iter().all(|w| w.len() >= n * 4) &&
+        (nreq == 0 || (nreq - 1).checked_mul(content_stride).and_then(|x| x.checked_add(slot.min(content_stride)))
+            .map_or(false, |e| e <= content.len() as u64))
+}
+
+/// [`read_ranges`] for requests that live on the device: `req_stream` (u32),
+/// `start` and `len` (u64) are device arrays of `nreq` entries, read by the
+/// GPU only; `nreq` and `max_len` are the capacity of the call (spare
+/// requests: length 0).  Request r's content goes to
+/// `content[r * content_stride..]`, its length to `content_len[r]` (u64, on
+/// the device).  The host work is O(1) and nothing is uploaded.  Enqueued on
+/// `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn read_ranges_planned(table: &DeviceBuffer, info: &TableInfo, req_stream: &DeviceBuffer, start: &DeviceBuffer,
+                           len: &DeviceBuffer, nreq: u64, max_len: u64, content: &mut DeviceBuffer,
+                           content_stride: u64, content_len: &mut DeviceBuffer, status: &mut DeviceBuffer,
+                           used: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    if !planned_fits(nreq, max_len, req_stream, start, len, content, content_stride, content_len, &[status, used]) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_qread()?;
+    check(unsafe {
+        ffi_qread::chipq_read_ranges_dev(table.ptr, info, req_stream.as_ptr() as *const u32,
+                                         start.as_ptr() as *const u64, len.as_ptr() as *const u64, nreq, max_len,
+                                         content.as_mut_ptr(), content_stride, content_len.as_mut_ptr() as *mut u64,
+                                         status.as_mut_ptr() as *mut u32, used.as_mut_ptr() as *mut u32, scratch.ptr,
+                                         scratch.len() as u64, stream.0)
+    })
+}
+
+/// [`read_ranges_vouched`] for requests that live on the device: the
+/// arguments of [`read_ranges_planned`], the vouch word per request and
+/// `flags` (0 or [`VREAD_STRICT`]) as there.
+#[allow(clippy::too_many_arguments)]
+pub fn read_ranges_vouched_planned(table: &DeviceBuffer, info: &TableInfo, req_stream: &DeviceBuffer,
+                                   start: &DeviceBuffer, len: &DeviceBuffer, nreq: u64, max_len: u64,
+                                   content: &mut DeviceBuffer, content_stride: u64, content_len: &mut DeviceBuffer,
+                                   status: &mut DeviceBuffer, used: &mut DeviceBuffer, vouch: &mut DeviceBuffer,
+                                   flags: u32, scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    if !planned_fits(nreq, max_len, req_stream, start, len, content, content_stride, content_len,
+                     &[status, used, vouch]) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_qread()?;
+    check(unsafe {
+        ffi_qread::chipq_read_ranges_vouched_dev(table.ptr, info, req_stream.as_ptr() as *const u32,
+                                                 start.as_ptr() as *const u64, len.as_ptr() as *const u64, nreq,
+                                                 max_len, content.as_mut_ptr(), content_stride,
+                                                 content_len.as_mut_ptr() as *mut u64, status.as_mut_ptr() as *mut u32,
+                                                 used.as_mut_ptr() as *mut u32, vouch.as_mut_ptr() as *mut u32, flags,
+                                                 scratch.ptr, scratch.len() as u64, stream.0)
+    })
 }
 
 #[cfg(test)]

@@ -358,6 +358,34 @@ FREAD_SIGNATURES = {
                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
 }
 
+# the qread header (include/carbonado_hip_qread.h): ranged reads planned on the
+# device from requests in device memory, an eleventh table of its own
+class TableInfo(ctypes.Structure):
+    """chipq_table_info: what the planned reads know of a stream table."""
+    _fields_ = [("nstreams", ctypes.c_uint64), ("max_chunks", ctypes.c_uint64), ("min_shard", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64)]
+
+
+c_infop = ctypes.POINTER(TableInfo)
+QREAD_SIGNATURES = {
+    "chipq_abi_version": (ctypes.c_int, []),
+    "chipq_stream_table_len": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "chipq_stream_table_dev": (ctypes.c_int, [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_void_p, c_u32p, c_u32p,
+                                              ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, c_infop,
+                                              ctypes.c_void_p]),
+    "chipq_read_scratch_len": (ctypes.c_uint64, [c_infop, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]),
+    "chipq_read_ranges_dev": (ctypes.c_int, [ctypes.c_void_p, c_infop, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "chipq_read_ranges_vouched_dev": (ctypes.c_int, [ctypes.c_void_p, c_infop, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                                     ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -380,7 +408,8 @@ def lib() -> ctypes.CDLL:
         l = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES,
                                   **READ_SIGNATURES, **VREAD_SIGNATURES, **ECIES_SIGNATURES,
-                                  **SNAP_SIGNATURES, **CREAD_SIGNATURES, **FREAD_SIGNATURES}.items():
+                                  **SNAP_SIGNATURES, **CREAD_SIGNATURES, **FREAD_SIGNATURES,
+                                  **QREAD_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

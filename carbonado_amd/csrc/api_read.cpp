@@ -4,12 +4,28 @@
 // every table are host code in read_plan.hpp; this file uploads the table into
 // the caller's scratch and enqueues KA's checks of the primary slices
 // (audit_kernels.hip) and the kernels of read_kernels.hip behind it.
-#include "api_common.hpp"
-#include "audit_kernels.hpp"
-#include "read_kernels.hpp"
+#include "api_read.hpp"
 
 using namespace chip;
 using namespace chip::api;
+
+namespace chip {
+namespace api {
+
+int read_enqueue_launches(const ReadLaunch &L, AuditLaunch A, hipStream_t s) {
+    if (L.nseg) {
+        A.total_units = 0;  // KA's checks of every segment's own slice
+        A.proofs = false;
+        A.status = L.rstat;
+        CHIP_HIP(audit_verify_launch(A, s));
+        CHIP_HIP(read_fallback_launch(L, nullptr, s));
+    }
+    CHIP_HIP(read_serve_launch(L, s));
+    return CHIP_OK;
+}
+
+}  // namespace api
+}  // namespace chip
 
 extern "C" {
 
@@ -45,17 +61,8 @@ int chipd_read_ranges_dev(const uint8_t *d_streams, const uint64_t *in_off, cons
     uint8_t *scr = static_cast<uint8_t *>(d_scratch);
     CHIP_HIP(h2d(c->stage, scr, p.ka.table.data(), p.ka.table.size(), s));
     const ReadLaunch L = read_launch_of(p, scr, d_status, d_used);
-    if (p.nseg) {
-        CHIP_HIP(hipMemsetAsync(L.rstat, 0, read::M * p.nseg * sizeof(uint32_t), s));
-        AuditLaunch A = audit_launch_of(p.ka, scr + p.lay.audit);  // KA's checks of every segment's own slice
-        A.total_units = 0;
-        A.proofs = false;
-        A.status = L.rstat;
-        CHIP_HIP(audit_verify_launch(A, s));
-        CHIP_HIP(read_fallback_launch(L, nullptr, s));
-    }
-    CHIP_HIP(read_serve_launch(L, s));
-    return CHIP_OK;
+    if (p.nseg) CHIP_HIP(hipMemsetAsync(L.rstat, 0, read::M * p.nseg * sizeof(uint32_t), s));
+    return read_enqueue_launches(L, audit_launch_of(p.ka, scr + p.lay.audit), s);
 }
 
 }  // extern "C"

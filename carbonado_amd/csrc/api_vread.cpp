@@ -5,9 +5,8 @@
 // caller's scratch and enqueues KA's two checks of the primary slices
 // (audit_kernels.hip, one launch each so that parents and chunks flag
 // different words), the kernels of vread_kernels.hip and KD's read kernel.
+#include "api_read.hpp"
 #include "api_vread.hpp"
-#include "audit_kernels.hpp"
-#include "vread_kernels.hpp"
 
 using namespace chip;
 using namespace chip::api;
@@ -28,20 +27,24 @@ int vread_enqueue(vread::Plan &vp, uint32_t *d_status, uint32_t *d_used, uint32_
     CHIP_HIP(h2d(c->stage, scr, p.ka.table.data(), p.ka.table.size(), s));
     VreadLaunch V{};
     V.rd = read_launch_of(p, scr, d_status, d_used);
-    const ReadLaunch &L = V.rd;
     V.pathw = reinterpret_cast<uint32_t *>(scr + vp.lay.path);
     V.contra = reinterpret_cast<uint32_t *>(scr + vp.lay.contra);
     V.vouch = d_vouch;
     V.strict = flags & CHIPV_STRICT;
-    if (p.nseg) {
-        CHIP_HIP(hipMemsetAsync(scr + vp.lay.zero_from(), 0, vp.lay.zero_len(), s));
-        AuditLaunch A = audit_launch_of(p.ka, scr + p.lay.audit);  // KA's checks of every segment's own slice:
+    if (p.nseg) CHIP_HIP(hipMemsetAsync(scr + vp.lay.zero_from(), 0, vp.lay.zero_len(), s));
+    return vread_enqueue_launches(V, audit_launch_of(p.ka, scr + p.lay.audit), s);
+}
+
+int vread_enqueue_launches(const VreadLaunch &V, AuditLaunch A, hipStream_t s) {
+    const ReadLaunch &L = V.rd;
+    if (L.nseg) {
+        const uint64_t prim_chunks = A.total_chunks;  // KA's checks of every segment's own slice:
         A.total_units = 0;
         A.proofs = false;
         A.total_chunks = 0;  // the parents into the path words,
         A.status = V.pathw;
         CHIP_HIP(audit_verify_launch(A, s));
-        A.total_parents = 0; A.total_chunks = p.prim_chunks;  // the chunks (and the header) into the chunk words
+        A.total_parents = 0; A.total_chunks = prim_chunks;  // the chunks (and the header) into the chunk words
         A.status = L.rstat;
         CHIP_HIP(audit_verify_launch(A, s));
         CHIP_HIP(read_fallback_launch(L, V.pathw, s));

@@ -42,23 +42,26 @@ using namespace bao;
 
 namespace audit {
 
-template <bool PROOF>
+// BOUND: `total` is a bound the host sized the grid by, not the number of items
+// (the device-planned reads, qread_plan.hpp): an item at or past the last
+// entry of the prefix array leaves too.
+template <bool PROOF, bool BOUND>
 __global__ __launch_bounds__(TPB) void audit_parent_kernel(const Req *reqs, const uint64_t *pre, uint32_t nreq,
                                                            uint64_t total, uint32_t *status) {
     const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= total) return;
+    if (i >= total || (BOUND && i >= pre[nreq])) return;
     const uint32_t r = prefix_find(pre, nreq, i);
     const Req a = reqs[r];
     if (!parent_ok<PROOF>(a, i - pre[r])) flag_mismatch(status, r);
 }
 
-template <bool PROOF>
+template <bool PROOF, bool BOUND>
 __global__ __launch_bounds__(TPB) void audit_chunk_kernel(const Req *reqs, const uint64_t *pre, uint32_t nreq,
                                                           uint64_t total, uint32_t *status) {
     __shared__ __attribute__((aligned(16))) uint32_t msg[QUADS][16];  // each quad's message block
     const int t = threadIdx.x;
     const uint64_t i = (uint64_t)blockIdx.x * QUADS + (t >> 2);
-    if (i >= total) return;  // whole quads leave; the kernel has no workgroup barrier
+    if (i >= total || (BOUND && i >= pre[nreq])) return;  // whole quads leave; the kernel has no workgroup barrier
     const uint32_t r = prefix_find(pre, nreq, i);
     const Req a = reqs[r];
     if (!chunk_ok<PROOF>(a, i - pre[r], msg, t)) flag_mismatch(status, r);
@@ -128,12 +131,16 @@ hipError_t audit_verify_launch(const AuditLaunch &L, hipStream_t stream) {
     using namespace audit;
     const uint32_t nreq = (uint32_t)L.nreq;
     if (L.total_parents) {
-        const auto k = L.proofs ? audit_parent_kernel<true> : audit_parent_kernel<false>;
+        const auto k = L.bounded  ? audit_parent_kernel<false, true>  // (the device-planned reads check streams)
+                       : L.proofs ? audit_parent_kernel<true, false>
+                                  : audit_parent_kernel<false, false>;
         hipLaunchKernelGGL(k, dim3(nblocks(L.total_parents, TPB)), dim3(TPB), 0, stream, L.reqs, L.parents, nreq,
                            L.total_parents, L.status);
     }
     if (L.total_chunks) {
-        const auto k = L.proofs ? audit_chunk_kernel<true> : audit_chunk_kernel<false>;
+        const auto k = L.bounded  ? audit_chunk_kernel<false, true>
+                       : L.proofs ? audit_chunk_kernel<true, false>
+                                  : audit_chunk_kernel<false, false>;
         hipLaunchKernelGGL(k, dim3(nblocks(L.total_chunks, QUADS)), dim3(TPB), 0, stream, L.reqs, L.chunks, nreq,
                            L.total_chunks, L.status);
     }

@@ -16,6 +16,7 @@ struct AuditLaunch {
     uint64_t nreq, total_parents, total_chunks, total_units;
     bool proofs;              // verify: nodes addressed in the request's proof, not in its stream
     uint32_t *status;         // verify: [nreq], zero at launch
+    bool bounded;             // the totals are bounds: the kernels also read the last prefix entry (streams only)
 };
 
 // The launch table of a plan whose uploaded table lies at `base` on the

@@ -47,11 +47,12 @@ static_assert(sizeof(Req) == 64, "record layout");
 struct Sel {
     uint64_t N, first, last, parents, proof_len, olen;
 };
-inline Sel select(uint64_t n, uint64_t index, uint64_t count) {
+AUDIT_HD Sel select(uint64_t n, uint64_t index, uint64_t count) {
     Sel s;
-    s.N = chunks(n);
+    s.N = rules::chunks(n);
     s.first = umin(index, s.N - 1);
-    s.last = std::max(s.first + 1, umin(index + count, s.N));
+    s.last = umin(index + count, s.N);
+    if (s.last < s.first + 1) s.last = s.first + 1;
     const uint64_t bytes = umin(n, s.last * 1024) - s.first * 1024;  // n = 0: the empty chunk
     s.parents = sel_parents(s.N, s.first, s.last);
     s.proof_len = 8 + 64 * s.parents + bytes;
@@ -110,11 +111,16 @@ inline uint64_t extract_units(uint64_t parents, uint64_t nchunks) { return 1 + 4
 
 // One request into the table; the prefix entries hold this request's counts
 // until finish() turns them into prefix sums.
-inline void put(Plan *p, uint64_t r, const Sel &s, uint64_t n, uint64_t src, uint64_t dst, uint64_t hash,
-                uint64_t units) {
-    Req &q = p->reqs()[r];
+AUDIT_HD Req req_of(const Sel &s, uint64_t n, uint64_t src, uint64_t dst, uint64_t hash) {
+    Req q;
     q.src = src; q.dst = dst; q.hash = hash; q.n = n;
     q.N = s.N; q.first = s.first; q.last = s.last; q.olen = s.olen;
+    return q;
+}
+
+inline void put(Plan *p, uint64_t r, const Sel &s, uint64_t n, uint64_t src, uint64_t dst, uint64_t hash,
+                uint64_t units) {
+    p->reqs()[r] = req_of(s, n, src, dst, hash);
     p->parents()[r] = s.parents;
     p->chunks()[r] = s.last - s.first;
     p->units()[r] = units;

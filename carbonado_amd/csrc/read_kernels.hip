@@ -48,26 +48,28 @@ using audit::TPB;
 static_assert(BLOCK == UNIT * TPB, "content bytes per workgroup");
 
 // items [fpar[g], fpar[g + 1]) are segment g's: 7 x the most parents any of its fallback slices selects
-template <bool PATH>
+// (BOUND, here and below: `total` or the grid is a bound the host sized the
+// launch by, and an item at or past the last prefix entry leaves too)
+template <bool PATH, bool BOUND>
 __global__ __launch_bounds__(TPB) void read_fallback_parent_kernel(const audit::Req *slices, const Seg *segs,
                                                                    const uint64_t *fpar, uint32_t nseg, uint64_t total,
                                                                    const uint32_t *pathw, uint32_t *rstat) {
     const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
-    if (i >= total) return;
+    if (i >= total || (BOUND && i >= fpar[nseg])) return;
     const uint32_t g = audit::prefix_find(fpar, nseg, i);
     if (own_ok<PATH>(rstat, pathw, g)) return;
     fallback_parent_item(slices, segs, fpar, nseg, i, g, rstat);
 }
 
 // items [7 pre[g], 7 pre[g + 1]) are segment g's, pre = KA's chunk prefix of the primary slices
-template <bool PATH>
+template <bool PATH, bool BOUND>
 __global__ __launch_bounds__(TPB) void read_fallback_chunk_kernel(const audit::Req *slices, const Seg *segs,
                                                                   const uint64_t *pre, uint32_t nseg, uint64_t total,
                                                                   const uint32_t *pathw, uint32_t *rstat) {
     __shared__ __attribute__((aligned(16))) uint32_t msg[QUADS][16];  // each quad's message block
     const int t = threadIdx.x;
     const uint64_t i = (uint64_t)blockIdx.x * QUADS + (t >> 2);
-    if (i >= total) return;  // whole quads leave; the kernel has no workgroup barrier
+    if (i >= total || (BOUND && i >= FALLBACKS * pre[nseg])) return;  // whole quads leave; no workgroup barrier
     const uint32_t g = audit::prefix_find(pre, nseg, i / FALLBACKS);
     if (own_ok<PATH>(rstat, pathw, g)) return;
     fallback_chunk_item(slices, segs, pre, nseg, i, g, rstat, msg, t);
@@ -120,9 +122,11 @@ __device__ __forceinline__ u32x4 gather16(const uint8_t *src, uint64_t ch0, uint
     return u32x4{x[0], x[1], x[2], x[3]};
 }
 
+template <bool BOUND>
 __global__ __launch_bounds__(TPB) void read_kernel(const Seg *segs, const uint64_t *blocks, uint32_t nseg,
                                                    const Served *served, const uint32_t *status) {
     __shared__ uint32_t tab[256];
+    if (BOUND && blockIdx.x >= blocks[nseg]) return;  // the whole workgroup
     const uint32_t g = audit::prefix_find<uint64_t>(blocks, nseg, blockIdx.x);
     const Seg a = segs[g];
     const Served how = served[g];
@@ -180,12 +184,18 @@ hipError_t read_fallback_launch(const ReadLaunch &L, const uint32_t *pathw, hipS
     const uint32_t nseg = (uint32_t)L.nseg;
     const uint64_t fb_chunks = FALLBACKS * L.prim_chunks;
     if (L.fb_parents) {
-        const auto k = pathw ? read_fallback_parent_kernel<true> : read_fallback_parent_kernel<false>;
+        const auto k = L.bounded ? (pathw ? read_fallback_parent_kernel<true, true>
+                                          : read_fallback_parent_kernel<false, true>)
+                                 : (pathw ? read_fallback_parent_kernel<true, false>
+                                          : read_fallback_parent_kernel<false, false>);
         hipLaunchKernelGGL(k, dim3(nblocks(L.fb_parents, TPB)), dim3(TPB), 0, stream, L.slices, L.segs, L.fpar, nseg,
                            L.fb_parents, pathw, L.rstat);
     }
     if (fb_chunks) {
-        const auto k = pathw ? read_fallback_chunk_kernel<true> : read_fallback_chunk_kernel<false>;
+        const auto k = L.bounded ? (pathw ? read_fallback_chunk_kernel<true, true>
+                                          : read_fallback_chunk_kernel<false, true>)
+                                 : (pathw ? read_fallback_chunk_kernel<true, false>
+                                          : read_fallback_chunk_kernel<false, false>);
         hipLaunchKernelGGL(k, dim3(nblocks(fb_chunks, QUADS)), dim3(TPB), 0, stream, L.slices, L.segs, L.chunks, nseg,
                            fb_chunks, pathw, L.rstat);
     }
@@ -203,8 +213,8 @@ hipError_t read_serve_launch(const ReadLaunch &L, hipStream_t stream) {
 hipError_t read_copy_launch(const ReadLaunch &L, hipStream_t stream) {
     using namespace read;
     if (L.total_blocks)
-        hipLaunchKernelGGL(read_kernel, dim3((unsigned)L.total_blocks), dim3(TPB), 0, stream, L.segs, L.blocks,
-                           (uint32_t)L.nseg, L.served, L.status);
+        hipLaunchKernelGGL(L.bounded ? read_kernel<true> : read_kernel<false>, dim3((unsigned)L.total_blocks),
+                           dim3(TPB), 0, stream, L.segs, L.blocks, (uint32_t)L.nseg, L.served, L.status);
     return hipGetLastError();
 }
 

@@ -22,6 +22,7 @@ struct ReadLaunch {
     uint64_t nreq, nseg, total_blocks;
     uint64_t prim_parents, prim_chunks, fb_parents;
     uint32_t *status, *used;     // the caller's: [nreq] each
+    bool bounded;                // the device-planned reads: nseg counts slots, the totals are bounds (qread_plan.hpp)
 };
 
 // The launch table of a plan whose uploaded table lies at the start of the

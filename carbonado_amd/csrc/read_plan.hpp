@@ -95,7 +95,7 @@ struct Range {
     uint64_t begin = 0, end = 0; // object bytes [begin, end); begin == end: empty
     uint32_t nseg = 0;
 };
-inline Range range_of(uint64_t C, uint32_t padding, uint64_t start, uint64_t len) {
+AUDIT_HD Range range_of(uint64_t C, uint32_t padding, uint64_t start, uint64_t len) {
     Range g;
     if (!C || padding > K * C) {
         g.status = CHIP_ERR_ZFEC;
@@ -179,7 +179,39 @@ inline uint64_t status_word(uint64_t nseg, uint64_t g, uint32_t p, uint32_t i) {
 }
 
 // 16-B units of the addresses [a, b), b > a: partial ones at either end count
-inline uint64_t units_of(uint64_t a, uint64_t b) { return (b - a / UNIT * UNIT + UNIT - 1) / UNIT; }
+AUDIT_HD uint64_t units_of(uint64_t a, uint64_t b) { return (b - a / UNIT * UNIT + UNIT - 1) / UNIT; }
+
+// One segment of a request and the work it brings: the request's object bytes
+// from x up to the end of their primary (or of the range, `end`) of a stream of
+// n = 8 C content bytes at `src`, handed out at `dst`.  The host plan below and
+// the kernel that plans reads on the device (qread_device.hpp) both cut here.
+struct SegWork {
+    audit::Sel sel;       // the segment's own slice: its window of chunks of the stream (olen 0)
+    uint64_t bytes;       // content bytes of the segment
+    uint64_t fb_parents;  // fallback parent items
+    uint64_t blocks;      // workgroups of the read kernel
+};
+AUDIT_HD SegWork cut_segment(uint64_t x, uint64_t end, uint64_t C, uint64_t n, uint64_t src, uint64_t dst, uint32_t r,
+                             Seg *sg) {
+    const uint64_t spc = C / 1024, pr = x / C, stop = audit::umin(end, (pr + 1) * C);
+    sg->src = src; sg->dst = dst; sg->N = (uint32_t)(M * spc); sg->spc = (uint32_t)spc;
+    sg->c0 = (uint32_t)(x - pr * C); sg->c1 = (uint32_t)(stop - pr * C);  // c1 <= C < 2^32
+    sg->p = (uint32_t)pr; sg->req = r;
+    const uint64_t w0 = sg->c0 / 1024, w1 = ((uint64_t)sg->c1 + 1023) / 1024;
+    SegWork w;
+    w.sel = audit::select(n, pr * spc + w0, w1 - w0);
+    w.sel.olen = 0;
+    uint64_t most = 0;
+    for (uint64_t i = 0; i < M; ++i)
+        if (i != pr) {
+            const uint64_t here = audit::sel_parents(w.sel.N, i * spc + w0, i * spc + w1);
+            if (here > most) most = here;
+        }
+    w.bytes = stop - x;
+    w.fb_parents = FALLBACKS * most;
+    w.blocks = (units_of(dst, dst + w.bytes) * UNIT + BLOCK - 1) / BLOCK;
+    return w;
+}
 
 // Addresses are plain integers here (base + offset).  Every INVALID_ARG of a
 // call is found before its first BAO_TRUNCATED is reported.
@@ -226,27 +258,17 @@ inline int plan_read(uintptr_t d_streams, const uint64_t *in_off, const uint64_t
         Req &q = p->reqs()[r];
         q.seg0 = (uint32_t)g; q.nseg = rg.nseg; q.status = rg.status; q.pad_ = 0;
         if (!rg.nseg) continue;
-        const uint64_t C = chunk_len[s], spc = C / 1024, src = d_streams + in_off[s];
+        const uint64_t C = chunk_len[s], src = d_streams + in_off[s];
         uint64_t dst = d_content + content_off[r];
         for (uint64_t x = rg.begin; x < rg.end; ++g) {
-            const uint64_t pr = x / C, stop = audit::umin(rg.end, (pr + 1) * C);
-            Seg &sg = p->segs()[g];
-            sg.src = src; sg.dst = dst; sg.N = (uint32_t)(M * spc); sg.spc = (uint32_t)spc;
-            sg.c0 = (uint32_t)(x - pr * C); sg.c1 = (uint32_t)(stop - pr * C);  // c1 <= C < 2^32
-            sg.p = (uint32_t)pr; sg.req = (uint32_t)r;
-            const uint64_t w0 = sg.c0 / 1024, w1 = ((uint64_t)sg.c1 + 1023) / 1024;
-            audit::Sel sel = audit::select(n[s], pr * spc + w0, w1 - w0);
-            sel.olen = 0;
-            audit::put(&p->ka, g, sel, n[s], src, 0, d_hash + 32 * s, 0);
-            uint64_t most = 0;
-            for (uint64_t i = 0; i < M; ++i)
-                if (i != pr) most = std::max(most, audit::sel_parents(sel.N, i * spc + w0, i * spc + w1));
+            const SegWork w = cut_segment(x, rg.end, C, n[s], src, dst, (uint32_t)r, &p->segs()[g]);
+            audit::put(&p->ka, g, w.sel, n[s], src, 0, d_hash + 32 * s, 0);
             p->fpar()[g] = fp;
-            fp += FALLBACKS * most;
+            fp += w.fb_parents;
             p->blocks()[g] = b;
-            b += (units_of(dst, dst + (stop - x)) * UNIT + BLOCK - 1) / BLOCK;
-            dst += stop - x;
-            x = stop;
+            b += w.blocks;
+            dst += w.bytes;
+            x += w.bytes;
         }
     }
     p->fpar()[nseg] = fp;

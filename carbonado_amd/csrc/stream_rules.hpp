@@ -12,11 +12,17 @@
 
 #include "../../include/carbonado_hip.h"
 
+#if defined(__HIPCC__)
+#define RULES_HD __host__ __device__ inline  // also compiled by the kernel that plans reads (qread_kernels.hip)
+#else
+#define RULES_HD inline
+#endif
+
 namespace chip {
 namespace rules {
 
 // ---- a bao stream of n content bytes ------------------------------------------
-inline uint64_t chunks(uint64_t n) { return n == 0 ? 1 : (n + 1023) / 1024; }
+RULES_HD uint64_t chunks(uint64_t n) { return n == 0 ? 1 : (n + 1023) / 1024; }
 inline uint64_t bao_len(uint64_t n) { return 8 + n + 64 * (chunks(n) - 1); }
 
 // content length of a bao stream of `len` bytes (bao_len is strictly

@@ -68,13 +68,15 @@ __device__ __forceinline__ uint32_t gf_comb4(uint32_t x0, uint32_t x1, uint32_t 
 }
 
 // items [pre[g], pre[g + 1]) are segment g's window chunks, pre = KA's chunk prefix of the primary slices
+// (BOUND: `total` is a bound the host sized the grid by; an item at or past pre[nseg] leaves too)
+template <bool BOUND>
 __global__ __launch_bounds__(TPB) void vread_vouch_kernel(const audit::Req *slices, const uint64_t *pre, uint32_t nseg,
                                                           uint64_t total, const read::Served *served,
                                                           const uint32_t *pathw, uint32_t *contra) {
     __shared__ __attribute__((aligned(16))) uint32_t msg[QUADS][16];  // each quad's message block
     const int t = threadIdx.x, q = t & 3, qd = t >> 2;
     const uint64_t i = (uint64_t)blockIdx.x * QUADS + qd;
-    if (i >= total) return;  // whole quads leave; the kernel has no workgroup barrier
+    if (i >= total || (BOUND && i >= pre[nseg])) return;  // whole quads leave; the kernel has no workgroup barrier
     const uint32_t g = audit::prefix_find(pre, nseg, i);
     const read::Served how = served[g];
     if (how.mode != read::REBUILT || pathw[g] != 0) return;  // nothing to vouch for, or nothing to compare with
@@ -125,6 +127,10 @@ __global__ __launch_bounds__(TPB) void vread_vouch_kernel(const audit::Req *slic
     if (want[q] != h0 || want[4 + q] != h1) flag_mismatch(contra, g);
 }
 
+// PLANNED (the device-planned reads, qread_kernels.hip): a request the plan
+// refused keeps the plan's status, which can be 1 there; the host plan's only
+// refusal is 7, which `failed` gives.
+template <bool PLANNED>
 __global__ __launch_bounds__(TPB) void vread_finish_kernel(const read::Req *reqs, const read::Seg *segs,
                                                            const read::Served *served, const uint32_t *pathw,
                                                            const uint32_t *contra, uint32_t nreq, uint32_t strict,
@@ -146,7 +152,8 @@ __global__ __launch_bounds__(TPB) void vread_finish_kernel(const read::Req *reqs
             v |= pathw[g] ? CHIPV_UNVOUCHED : contra[g] ? CHIPV_CONTRADICTED : CHIPV_VOUCHED;
         }
     }
-    const uint32_t st = v & CHIPV_CONTRADICTED                        ? (uint32_t)CHIP_ERR_BAO_HASH_MISMATCH
+    const uint32_t st = PLANNED && rq.status                          ? rq.status  // refused by the plan: no segment
+                        : v & CHIPV_CONTRADICTED                      ? (uint32_t)CHIP_ERR_BAO_HASH_MISMATCH
                         : failed || (strict && (v & CHIPV_UNVOUCHED)) ? (uint32_t)CHIP_ERR_ZFEC
                                                                       : 0u;
     status[r] = st;
@@ -164,8 +171,9 @@ hipError_t vread_vouch_launch(const VreadLaunch &L, hipStream_t stream) {
         hipLaunchKernelGGL(vread_resolve_kernel, dim3(nblocks(nseg, TPB)), dim3(TPB), 0, stream, R.segs, R.masks,
                            R.rstat, L.pathw, nseg, R.served);
     if (R.prim_chunks)
-        hipLaunchKernelGGL(vread_vouch_kernel, dim3(nblocks(R.prim_chunks, QUADS)), dim3(TPB), 0, stream, R.slices,
-                           R.chunks, nseg, R.prim_chunks, R.served, L.pathw, L.contra);
+        hipLaunchKernelGGL(R.bounded ? vread_vouch_kernel<true> : vread_vouch_kernel<false>,
+                           dim3(nblocks(R.prim_chunks, QUADS)), dim3(TPB), 0, stream, R.slices, R.chunks, nseg,
+                           R.prim_chunks, R.served, L.pathw, L.contra);
     return hipGetLastError();
 }
 
@@ -173,8 +181,9 @@ hipError_t vread_finish_launch(const VreadLaunch &L, hipStream_t stream) {
     using namespace vread;
     const ReadLaunch &R = L.rd;
     if (R.nreq)
-        hipLaunchKernelGGL(vread_finish_kernel, dim3(nblocks(R.nreq, TPB)), dim3(TPB), 0, stream, R.reqs, R.segs,
-                           R.served, L.pathw, L.contra, (uint32_t)R.nreq, L.strict, R.status, R.used, L.vouch);
+        hipLaunchKernelGGL(R.bounded ? vread_finish_kernel<true> : vread_finish_kernel<false>,
+                           dim3(nblocks(R.nreq, TPB)), dim3(TPB), 0, stream, R.reqs, R.segs, R.served, L.pathw, L.contra,
+                           (uint32_t)R.nreq, L.strict, R.status, R.used, L.vouch);
     return hipGetLastError();
 }
 

@@ -655,6 +655,100 @@ def read_ranges_vouched(streams: torch.Tensor, in_off, in_len, hashes: torch.Ten
     return clen[:nreq].tolist()
 
 
+# ---- ranged reads planned on the device (include/carbonado_hip_qread.h): the
+# requests are device tensors, a kernel plans them, nothing is uploaded per call
+
+class StreamTable:
+    """The resident description of a set of streams (stream_table): the device
+    table and what the planned reads know of it on the host."""
+
+    def __init__(self, table: torch.Tensor, info: "_lib.TableInfo"):
+        self.table, self.info = table, info
+
+    nstreams = property(lambda self: self.info.nstreams)
+    max_chunks = property(lambda self: self.info.max_chunks)
+    min_shard = property(lambda self: self.info.min_shard)
+
+
+def stream_table(streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len) -> StreamTable:
+    """Describe resident streams once (the stream arguments of read_ranges):
+    one record per stream and the share-selection table, uploaded on the
+    current stream.  The table serves every later read_ranges_planned call
+    while the streams and hashes stay where they are; an in-place scrub does not
+    invalidate it."""
+    assert streams.is_cuda and hashes.is_cuda and streams.dtype == torch.uint8 and streams.dim() == 1
+    assert streams.is_contiguous() and hashes.is_contiguous()
+    ioff, pioff, nstreams = _arr(in_off)
+    ilen, pilen, nl = _arr(in_len)
+    pad, ppad, npad = _arr(padding, np.uint32)
+    cl, pcl, ncl = _arr(chunk_len, np.uint32)
+    assert nl == nstreams == npad == ncl
+    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
+    table = torch.empty(_lib.lib().chipq_stream_table_len(nstreams), dtype=torch.uint8, device=streams.device)
+    info = _lib.TableInfo()
+    check(_lib.lib().chipq_stream_table_dev(_p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams, _p(table),
+                                            table.numel(), ctypes.byref(info), _stream()))
+    return StreamTable(table, info)
+
+
+def planned_read_scratch(table: StreamTable, nreq: int, max_len: int, vouched: bool = False,
+                         device=None) -> torch.Tensor:
+    """Scratch of a read_ranges_planned (vouched: read_ranges_vouched_planned)
+    call of capacity (nreq, max_len) over `table`."""
+    size = _lib.lib().chipq_read_scratch_len(ctypes.byref(table.info), nreq, max_len, 1 if vouched else 0)
+    if nreq and not size:
+        raise ValueError("the call would refuse this capacity")
+    return torch.empty(size, dtype=torch.uint8, device=device or table.table.device)
+
+
+def _planned_args(table, req_stream, start, length, max_len, content, content_stride, content_len, words, scratch):
+    nreq = req_stream.numel()
+    assert start.numel() == length.numel() == content_len.numel() == nreq
+    assert req_stream.element_size() == 4 and start.element_size() == length.element_size() == 8
+    assert content_len.element_size() == 8 and content.dtype == torch.uint8 and content.dim() == 1
+    for t in (req_stream, start, length, content, content_len, scratch, table.table) + tuple(words):
+        assert t.is_cuda and t.is_contiguous()
+    for t in words:
+        assert t.numel() >= nreq and t.element_size() == 4
+    assert nreq == 0 or content.numel() >= (nreq - 1) * content_stride + min(content_stride, (max_len + 15) // 16 * 16)
+    return nreq
+
+
+def read_ranges_planned(table: StreamTable, req_stream: torch.Tensor, start: torch.Tensor, length: torch.Tensor,
+                        max_len: int, content: torch.Tensor, content_stride: int, content_len: torch.Tensor,
+                        status: torch.Tensor, used: torch.Tensor, scratch: torch.Tensor) -> None:
+    """read_ranges for requests that live on the device: req_stream (int32 /
+    uint32), start and length (int64 / uint64) are device tensors of nreq
+    entries, read by the GPU only; nreq and max_len are the capacity of the
+    call (spare requests: length 0).  Request r's content goes to
+    content[r * content_stride :], its length to content_len[r] (device int64 /
+    uint64).  status: 1 for a request the device refuses (stream index, range
+    above 2^53, content longer than max_len), else read_ranges' status, used
+    word and bytes.  The host work is O(1) and nothing is uploaded: after one
+    warm-up call the call can be captured into a graph and replayed with the
+    request tensors rewritten in place.  Enqueued on the current stream."""
+    nreq = _planned_args(table, req_stream, start, length, max_len, content, content_stride, content_len,
+                         (status, used), scratch)
+    check(_lib.lib().chipq_read_ranges_dev(_p(table.table), ctypes.byref(table.info), _p(req_stream), _p(start),
+                                           _p(length), nreq, max_len, _p(content), content_stride, _p(content_len),
+                                           _p(status), _p(used), _p(scratch), scratch.numel(), _stream()))
+
+
+def read_ranges_vouched_planned(table: StreamTable, req_stream: torch.Tensor, start: torch.Tensor,
+                                length: torch.Tensor, max_len: int, content: torch.Tensor, content_stride: int,
+                                content_len: torch.Tensor, status: torch.Tensor, used: torch.Tensor,
+                                vouch: torch.Tensor, scratch: torch.Tensor, flags: int = 0) -> None:
+    """read_ranges_vouched for requests that live on the device: the arguments
+    of read_ranges_planned, the vouch word per request and flags (0 or
+    VREAD_STRICT) as there."""
+    nreq = _planned_args(table, req_stream, start, length, max_len, content, content_stride, content_len,
+                         (status, used, vouch), scratch)
+    check(_lib.lib().chipq_read_ranges_vouched_dev(_p(table.table), ctypes.byref(table.info), _p(req_stream),
+                                                   _p(start), _p(length), nreq, max_len, _p(content), content_stride,
+                                                   _p(content_len), _p(status), _p(used), _p(vouch), flags,
+                                                   _p(scratch), scratch.numel(), _stream()))
+
+
 # ---- AES-256-GCM over resident messages (include/carbonado_hip_ecies.h): the
 # data half of the Ecies stage, one ragged batch per call
 
