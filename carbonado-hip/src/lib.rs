@@ -31,6 +31,7 @@ mod ffi_snap;
 mod ffi_cread;
 mod ffi_fread;
 mod ffi_qread;
+mod ffi_kread;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -2089,6 +2090,82 @@ pub fn read_ranges_vouched_planned(table: &DeviceBuffer, info: &TableInfo, req_s
                                                  content_len.as_mut_ptr() as *mut u64, status.as_mut_ptr() as *mut u32,
                                                  used.as_mut_ptr() as *mut u32, vouch.as_mut_ptr() as *mut u32, flags,
                                                  scratch.ptr, scratch.len() as u64, stream.0)
+    })
+}
+
+fn abi_kread() -> Result<()> {
+    abi_qread()?;
+    abi_cread()?;
+    match unsafe { ffi_kread::chipk_abi_version() } {
+        ffi_kread::CHIPK_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// Bytes of device memory the key table of `nstreams` streams needs ([`key_table`]).
+pub fn key_table_len(nstreams: u64) -> u64 {
+    unsafe { ffi_kread::chipk_key_table_len(nstreams) }
+}
+
+/// Expand the keys of resident level-13 streams once (`keys`, `ivs` and
+/// `key_status` as [`stream_keys`] gave them) into `table`, for every later
+/// [`read_plain_ranges_planned`] call: round keys and J0 per stream, zeros for
+/// a stream whose key status is not 0.  The raw keys pass through a staging
+/// part of the table that is zeros again once the enqueued work is done; the
+/// round keys STAY in `table` until [`wipe_key_table`].  Enqueued on `stream`.
+pub fn key_table(keys: &[u8], ivs: &[u8], key_status: Option<&[u32]>, table: &mut DeviceBuffer, stream: Stream)
+                 -> Result<()> {
+    let count = keys.len() / 32;
+    if keys.len() != 32 * count || ivs.len() != 16 * count || key_status.map_or(false, |k| k.len() != count) ||
+        (table.len() as u64) < key_table_len(count as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_kread()?;
+    check(unsafe {
+        ffi_kread::chipk_key_table_dev(keys.as_ptr(), ivs.as_ptr(), key_status.map_or(ptr::null(), |k| k.as_ptr()),
+                                       count as u64, table.ptr, table.len() as u64, stream.0)
+    })
+}
+
+/// Zeros over the whole key table, enqueued on `stream` behind the reads that use it.
+pub fn wipe_key_table(table: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    abi_kread()?;
+    check(unsafe { ffi_kread::chipk_key_table_wipe_dev(table.ptr, table.len() as u64, stream.0) })
+}
+
+/// Scratch of a [`read_plain_ranges_planned`] call of capacity (`nreq`,
+/// `max_len`); 0 where the call would refuse it.
+pub fn planned_plain_read_scratch_len(info: &TableInfo, nreq: u64, max_len: u64) -> u64 {
+    unsafe { ffi_kread::chipk_read_scratch_len(info, nreq, max_len) }
+}
+
+/// [`read_plain_ranges`] for requests that live on the device: the arguments
+/// of [`read_ranges_vouched_planned`] with requests in PLAINTEXT bytes of
+/// level-13 streams, over the stream table and the key table ([`key_table`])
+/// of the same streams.  A request the device refuses has status 1; a request
+/// on a stream whose key status is not 0 has that status, zeros over its
+/// clipped range, used 0 and vouch 0.  Kernel launches only; enqueued on
+/// `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn read_plain_ranges_planned(table: &DeviceBuffer, info: &TableInfo, key_table: &DeviceBuffer,
+                                 req_stream: &DeviceBuffer, start: &DeviceBuffer, len: &DeviceBuffer, nreq: u64,
+                                 max_len: u64, content: &mut DeviceBuffer, content_stride: u64,
+                                 content_len: &mut DeviceBuffer, status: &mut DeviceBuffer, used: &mut DeviceBuffer,
+                                 vouch: &mut DeviceBuffer, flags: u32, scratch: &mut DeviceBuffer, stream: Stream)
+                                 -> Result<()> {
+    if !planned_fits(nreq, max_len, req_stream, start, len, content, content_stride, content_len,
+                     &[status, used, vouch]) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_kread()?;
+    check(unsafe {
+        ffi_kread::chipk_read_ranges_dev(table.ptr, info, key_table.ptr, key_table.len() as u64,
+                                         req_stream.as_ptr() as *const u32, start.as_ptr() as *const u64,
+                                         len.as_ptr() as *const u64, nreq, max_len, content.as_mut_ptr(),
+                                         content_stride, content_len.as_mut_ptr() as *mut u64,
+                                         status.as_mut_ptr() as *mut u32, used.as_mut_ptr() as *mut u32,
+                                         vouch.as_mut_ptr() as *mut u32, flags, scratch.ptr, scratch.len() as u64,
+                                         stream.0)
     })
 }
 

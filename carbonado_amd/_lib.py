@@ -386,6 +386,23 @@ QREAD_SIGNATURES = {
                                                      ctypes.c_void_p]),
 }
 
+# the kread header (include/carbonado_hip_kread.h): plaintext ranged reads of
+# level-13 streams planned on the device over a resident key table, a twelfth
+# table of its own
+KREAD_SIGNATURES = {
+    "chipk_abi_version": (ctypes.c_int, []),
+    "chipk_key_table_len": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "chipk_key_table_dev": (ctypes.c_int, [c_u8p, c_u8p, c_u32p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_void_p]),
+    "chipk_key_table_wipe_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "chipk_read_scratch_len": (ctypes.c_uint64, [c_infop, ctypes.c_uint64, ctypes.c_uint64]),
+    "chipk_read_ranges_dev": (ctypes.c_int, [ctypes.c_void_p, c_infop, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -409,7 +426,7 @@ def lib() -> ctypes.CDLL:
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES,
                                   **READ_SIGNATURES, **VREAD_SIGNATURES, **ECIES_SIGNATURES,
                                   **SNAP_SIGNATURES, **CREAD_SIGNATURES, **FREAD_SIGNATURES,
-                                  **QREAD_SIGNATURES}.items():
+                                  **QREAD_SIGNATURES, **KREAD_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

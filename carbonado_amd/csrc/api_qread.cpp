@@ -7,31 +7,17 @@
 // (qread_kernels.hip) and the launches of chipd_read_ranges_dev /
 // chipv_read_ranges_dev behind it (api_read.hpp).  Kernels only: no upload, no
 // memset, no synchronisation, no allocation after the thread's first call.
-#include "api_read.hpp"
-#include "qread_kernels.hpp"
+// read_planned is declared in api_qread.hpp: api_kread.cpp runs it over
+// requests its own kernel rewrote.
+#include "api_qread.hpp"
 
 using namespace chip;
 using namespace chip::api;
 
-namespace {
+namespace chip {
+namespace api {
 
-struct Call {
-    const void *d_table;
-    const chipq_table_info *info;
-    const uint32_t *d_req_stream;
-    const uint64_t *d_start, *d_len;
-    uint64_t nreq, max_len;
-    uint8_t *d_content;
-    uint64_t content_stride;
-    uint64_t *d_content_len;
-    uint32_t *d_status, *d_used, *d_vouch;
-    uint32_t flags;
-    void *d_scratch;
-    uint64_t scratch_len;
-    void *stream;
-};
-
-int read_planned(const Call &a, bool vouched) {
+int read_planned(const QreadCall &a, bool vouched) {
     if (a.nreq == 0) return CHIP_OK;
     qread::Geometry g;
     qread::ScratchLayout lay;
@@ -95,7 +81,8 @@ int read_planned(const Call &a, bool vouched) {
     return vread_enqueue_launches(V, A, s);
 }
 
-}  // namespace
+}  // namespace api
+}  // namespace chip
 
 extern "C" {
 
@@ -131,7 +118,7 @@ int chipq_read_ranges_dev(const void *d_table, const chipq_table_info *info, con
                           const uint64_t *d_start, const uint64_t *d_len, uint64_t nreq, uint64_t max_len,
                           uint8_t *d_content, uint64_t content_stride, uint64_t *d_content_len, uint32_t *d_status,
                           uint32_t *d_used, void *d_scratch, uint64_t scratch_len, void *stream) {
-    return read_planned(Call{d_table, info, d_req_stream, d_start, d_len, nreq, max_len, d_content, content_stride,
+    return read_planned(QreadCall{d_table, info, d_req_stream, d_start, d_len, nreq, max_len, d_content, content_stride,
                              d_content_len, d_status, d_used, nullptr, 0, d_scratch, scratch_len, stream},
                         false);
 }
@@ -141,7 +128,7 @@ int chipq_read_ranges_vouched_dev(const void *d_table, const chipq_table_info *i
                                   uint8_t *d_content, uint64_t content_stride, uint64_t *d_content_len,
                                   uint32_t *d_status, uint32_t *d_used, uint32_t *d_vouch, uint32_t flags,
                                   void *d_scratch, uint64_t scratch_len, void *stream) {
-    return read_planned(Call{d_table, info, d_req_stream, d_start, d_len, nreq, max_len, d_content, content_stride,
+    return read_planned(QreadCall{d_table, info, d_req_stream, d_start, d_len, nreq, max_len, d_content, content_stride,
                              d_content_len, d_status, d_used, d_vouch, flags, d_scratch, scratch_len, stream},
                         true);
 }

@@ -1067,6 +1067,74 @@ def read_plain_ranges(keys, ivs, key_status, streams: torch.Tensor, in_off, in_l
     return clen[:nreq].tolist()
 
 
+# ---- plaintext reads of level-13 streams planned on the device
+# (include/carbonado_hip_kread.h): the keys are expanded once into a resident
+# table, the requests are device tensors, nothing is uploaded per call
+
+class KeyTable:
+    """The resident keys of a set of level-13 streams (key_table): round keys,
+    J0 and the key_status word of every stream, in device memory until
+    wipe_key_table."""
+
+    def __init__(self, table: torch.Tensor, nstreams: int):
+        self.table, self.nstreams = table, nstreams
+
+
+def key_table(keys, ivs, key_status, device=None) -> KeyTable:
+    """Expand the keys of resident level-13 streams once (keys, ivs and
+    key_status as stream_keys gave them; key_status may be None): one record of
+    round keys and J0 per stream, zeros for a stream whose key_status is not 0.
+    The raw keys are uploaded into a staging part of the table, which is zeros
+    again once the enqueued work is done.  The round keys STAY on the device, in
+    the returned table, until wipe_key_table.  Enqueued on the current stream."""
+    k = np.ascontiguousarray(np.frombuffer(bytes(keys), dtype=np.uint8) if not isinstance(keys, np.ndarray) else keys,
+                             dtype=np.uint8).reshape(-1)
+    nstreams = k.size // 32
+    kk, pk, vv, pv = _gcm_keys(k, ivs, nstreams)
+    pks = None
+    if key_status is not None:
+        ks, pks, nks = _arr(key_status, np.uint32)
+        assert nks == nstreams
+    table = torch.empty(_lib.lib().chipk_key_table_len(nstreams), dtype=torch.uint8, device=device or "cuda")
+    check(_lib.lib().chipk_key_table_dev(pk, pv, pks, nstreams, _p(table), table.numel(), _stream()))
+    return KeyTable(table, nstreams)
+
+
+def wipe_key_table(table: KeyTable) -> None:
+    """Zeros over the whole key table, enqueued on the current stream behind the reads that use it."""
+    check(_lib.lib().chipk_key_table_wipe_dev(_p(table.table), table.table.numel(), _stream()))
+
+
+def planned_plain_read_scratch(table: StreamTable, nreq: int, max_len: int, device=None) -> torch.Tensor:
+    """Scratch of a read_plain_ranges_planned call of capacity (nreq, max_len) over `table`."""
+    size = _lib.lib().chipk_read_scratch_len(ctypes.byref(table.info), nreq, max_len)
+    if nreq and not size:
+        raise ValueError("the call would refuse this capacity")
+    return torch.empty(size, dtype=torch.uint8, device=device or table.table.device)
+
+
+def read_plain_ranges_planned(table: StreamTable, key_table: KeyTable, req_stream: torch.Tensor, start: torch.Tensor,
+                              length: torch.Tensor, max_len: int, content: torch.Tensor, content_stride: int,
+                              content_len: torch.Tensor, status: torch.Tensor, used: torch.Tensor, vouch: torch.Tensor,
+                              scratch: torch.Tensor, flags: int = 0) -> None:
+    """read_plain_ranges for requests that live on the device: the arguments of
+    read_ranges_vouched_planned with requests in PLAINTEXT bytes of level-13
+    streams, over the stream table and a key table of the same streams.
+    status: 1 for a request the device refuses (as read_ranges_planned; a start
+    above 2^53 - 97; a range that ends above 2^36 - 32), the stream's key_status
+    where that is not 0 (zeros over the clipped range, used 0, vouch 0), else
+    read_plain_ranges' status, words and bytes.  Kernel launches only: after one
+    warm-up call the call can be captured into a graph and replayed with the
+    request tensors rewritten in place.  Enqueued on the current stream."""
+    nreq = _planned_args(table, req_stream, start, length, max_len, content, content_stride, content_len,
+                         (status, used, vouch), scratch)
+    assert key_table.table.is_cuda and key_table.table.is_contiguous() and key_table.nstreams == table.nstreams
+    check(_lib.lib().chipk_read_ranges_dev(_p(table.table), ctypes.byref(table.info), _p(key_table.table),
+                                           key_table.table.numel(), _p(req_stream), _p(start), _p(length), nreq,
+                                           max_len, _p(content), content_stride, _p(content_len), _p(status),
+                                           _p(used), _p(vouch), flags, _p(scratch), scratch.numel(), _stream()))
+
+
 # ---- snappy on the device (include/carbonado_hip_snap.h): the framing format
 # of encoding::snap / decoding::snap over ragged batches, bit-exact with
 # chip_snap_compress, and the one-call forms of formats 6, 7, 10, 11, 14, 15
