@@ -255,27 +255,41 @@ def decode_host_batch(fmt: int, enc: torch.Tensor, in_len, hashes: torch.Tensor,
 # lengths in one call; `inp` / `out` / `enc` are flat uint8 buffers and each
 # object has its own offset and length (host sequences of ints)
 
-def _u64(xs):
-    xs = [int(x) for x in xs]
-    return (ctypes.c_uint64 * max(len(xs), 1))(*xs), len(xs)
+# Everything below marshals through one vocabulary (_marshal.py).  Its rule:
+# bind what a helper returns and keep it until the library call has returned;
+# the arrays are what keeps the pointers valid.
+from ._marshal import (_arr, _cols, _fits, _flat, _gcm_keys, _hashes, _opt, _out, _ragged,  # noqa: E402
+                       _request_args, _resident, _scratch, _stream_args, _words)
+
+
+def _encode_outputs(count: int):
+    """(encoded lengths, their pointer, EncodeInfoC array) for an encode call to fill"""
+    olen, polen = _out(count)
+    return olen, polen, (_lib.EncodeInfoC * max(count, 1))()
+
+
+def _encoded(olen, info, ooff, out):
+    """what a ragged encode returns, once the encodings are known to lie inside out"""
+    from .structs import EncodeInfo
+    assert _fits(ooff, olen, out.numel())
+    return olen.tolist(), [EncodeInfo.from_c(info[o]) for o in range(olen.size)]
 
 
 def ragged_layout(fmt: int, sizes, align: int = 256, stream_offset: int = STREAM_OFFSET):
     """Where encode_ragged's caller should put each object in one output
     buffer (host only): rows rounded up to `align`, each encoding
     `stream_offset` bytes into its row.  Returns (out_off, out_len, total)."""
-    n, count = _u64(sizes)
-    off, ln, total = (ctypes.c_uint64 * max(count, 1))(), (ctypes.c_uint64 * max(count, 1))(), ctypes.c_uint64()
-    check(_lib.lib().chipx_ragged_layout(fmt, n, count, align, stream_offset, off, ln, ctypes.byref(total)))
-    return list(off)[:count], list(ln)[:count], total.value
+    n, pn, count = _arr(sizes)
+    (off, poff), (ln, pln), total = _out(count), _out(count), ctypes.c_uint64()
+    check(_lib.lib().chipx_ragged_layout(fmt, pn, count, align, stream_offset, poff, pln, ctypes.byref(total)))
+    return off.tolist(), ln.tolist(), total.value
 
 
 def ragged_scratch(fmt: int, lens, decode: bool = False, device=None) -> torch.Tensor:
     """Scratch of a ragged call over objects of these lengths (input lengths
     of encode_ragged, encoded lengths of decode_ragged)."""
-    ln, count = _u64(lens)
-    size = _lib.lib().chipx_ragged_scratch_len(fmt, ln, count, int(decode))
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    ln, pln, count = _arr(lens)
+    return _scratch(_lib.lib().chipx_ragged_scratch_len(fmt, pln, count, int(decode)), device)
 
 
 def encode_ragged(fmt: int, inp: torch.Tensor, in_off, sizes, out: torch.Tensor, out_off, hashes: torch.Tensor,
@@ -284,21 +298,14 @@ def encode_ragged(fmt: int, inp: torch.Tensor, in_off, sizes, out: torch.Tensor,
     inp[in_off[o] : in_off[o] + sizes[o]] into out[out_off[o] :] (offsets as
     ragged_layout gives them), its hash to hashes[o] (uint8 [count, 32]).
     Returns (encoded length per object, EncodeInfo per object)."""
-    from .structs import EncodeInfo
-    assert inp.is_cuda and out.is_cuda and hashes.is_cuda and scratch.is_cuda
-    assert inp.dtype == out.dtype == torch.uint8 and inp.dim() == out.dim() == 1
-    assert inp.is_contiguous() and out.is_contiguous() and hashes.is_contiguous()
-    ioff, count = _u64(in_off)
-    n, _ = _u64(sizes)
-    ooff, _ = _u64(out_off)
-    assert len(sizes) == count == len(out_off) and hashes.numel() >= 32 * count
-    assert all(int(a) + int(b) <= inp.numel() for a, b in zip(in_off, sizes))
-    olen = (ctypes.c_uint64 * max(count, 1))()
-    info = (_lib.EncodeInfoC * max(count, 1))()
-    check(_lib.lib().chipx_encode_ragged_dev(fmt, _p(inp), ioff, n, count, _p(out), ooff, olen, _p(hashes), info,
+    _flat(inp, out)
+    _resident(scratch)
+    (ioff, n, ooff), (pioff, pn, pooff), count = _ragged(inp, in_off, sizes, out, out_off, room=None)
+    _hashes(hashes, count)
+    olen, polen, info = _encode_outputs(count)
+    check(_lib.lib().chipx_encode_ragged_dev(fmt, _p(inp), pioff, pn, count, _p(out), pooff, polen, _p(hashes), info,
                                              _p(scratch), _stream()))
-    assert all(int(a) + b <= out.numel() for a, b in zip(out_off, list(olen)[:count]))
-    return list(olen)[:count], [EncodeInfo.from_c(info[o]) for o in range(count)]
+    return _encoded(olen, info, ooff, out)
 
 
 def decode_ragged(fmt: int, enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, out: torch.Tensor,
@@ -307,20 +314,17 @@ def decode_ragged(fmt: int, enc: torch.Tensor, in_off, in_len, hashes: torch.Ten
     hashes[o] and padding[o] into out[out_off[o] :]; status int32 / uint32
     [count] on the device (0, or 5 = that object's hash mismatch).  Returns
     the decoded length per object."""
-    assert enc.is_cuda and out.is_cuda and hashes.is_cuda and status.is_cuda and scratch.is_cuda
-    assert enc.dtype == out.dtype == torch.uint8 and enc.dim() == out.dim() == 1
-    assert enc.is_contiguous() and out.is_contiguous() and hashes.is_contiguous()
-    ioff, count = _u64(in_off)
-    ilen, _ = _u64(in_len)
-    ooff, _ = _u64(out_off)
-    pads = (ctypes.c_uint32 * max(count, 1))(*[int(x) for x in padding])
-    assert len(in_len) == count == len(out_off) == len(padding) and status.numel() >= count
-    assert all(int(a) + int(b) <= enc.numel() for a, b in zip(in_off, in_len))
-    olen = (ctypes.c_uint64 * max(count, 1))()
-    check(_lib.lib().chipx_decode_ragged_dev(fmt, _p(enc), ioff, ilen, count, _p(hashes), pads, _p(out), ooff, olen,
+    _flat(enc, out)
+    _resident(scratch)
+    (ioff, ilen, ooff, pad), (pioff, pilen, pooff, ppad), count = _ragged(enc, in_off, in_len, out, out_off, padding,
+                                                                          kinds="I", room=None)
+    _hashes(hashes, count)
+    _words(count, status, size=None, contiguous=False)
+    olen, polen = _out(count)
+    check(_lib.lib().chipx_decode_ragged_dev(fmt, _p(enc), pioff, pilen, count, _p(hashes), ppad, _p(out), pooff, polen,
                                              _p(status), _p(scratch), _stream()))
-    assert all(int(a) + b <= out.numel() for a, b in zip(out_off, list(olen)[:count]))
-    return list(olen)[:count]
+    assert _fits(ooff, olen, out.numel())
+    return olen.tolist()
 
 
 # ---- slice audits (include/carbonado_hip_audit.h): extract_slice /
@@ -328,20 +332,6 @@ def decode_ragged(fmt: int, enc: torch.Tensor, in_off, in_len, hashes: torch.Ten
 # `streams`, `proofs` and `content` are flat uint8 buffers; a request r is
 # (req_stream[r], index[r], count[r]) in units of 1024 bytes, as
 # decoding.verify_slice takes them
-
-def _arr(xs, dtype=np.uint64):
-    """(array, its pointer, its length) of a host sequence or numpy array; the
-    array stays referenced by the caller for the duration of the call."""
-    a = np.ascontiguousarray(xs, dtype=dtype).reshape(-1)
-    keep = a if a.size else np.zeros(1, dtype=dtype)
-    return keep, keep.ctypes.data_as(_lib.c_u64p if dtype == np.uint64 else _lib.c_u32p), int(a.size)
-
-
-def _fits(off, length, numel: int) -> bool:
-    """every range [off[r], off[r] + length[r]) lies inside a buffer of numel bytes"""
-    o, m = off[:length.size], np.uint64(numel)
-    return bool((o <= m).all() and (length <= m - np.minimum(o, m)).all())
-
 
 def _stream_content_lens(in_len):
     """Content bytes of bao streams of in_len bytes: x = len - 8 = n + 64 (N - 1)
@@ -366,21 +356,17 @@ def slice_layout(content_lens, index, count, align: int = 16):
     (proof_off, proof_len, content_off, content_len, proof_total,
     content_total): offsets into one proof and one content buffer, each range
     on a multiple of `align` (a multiple of 16)."""
-    n, pn, nreq = _arr(content_lens)
-    idx, pidx, ni = _arr(index)
-    cnt, pcnt, nc = _arr(count)
-    assert ni == nreq == nc
-    outs = [np.zeros(max(nreq, 1), dtype=np.uint64) for _ in range(4)]
+    cols, (pn, pidx, pcnt), nreq = _cols("QQQ", content_lens, index, count)
+    outs = [_out(nreq) for _ in range(4)]
     pt, ct = ctypes.c_uint64(), ctypes.c_uint64()
-    check(_lib.lib().chipa_slice_layout(pn, pidx, pcnt, nreq, align, *[o.ctypes.data_as(_lib.c_u64p) for o in outs],
+    check(_lib.lib().chipa_slice_layout(pn, pidx, pcnt, nreq, align, *[p for _, p in outs],
                                         ctypes.byref(pt), ctypes.byref(ct)))
-    return (*[o[:nreq].tolist() for o in outs], pt.value, ct.value)
+    return (*[o.tolist() for o, _ in outs], pt.value, ct.value)
 
 
 def audit_scratch(nstreams: int, nreq: int, device=None) -> torch.Tensor:
     """Scratch of an extract_slices / verify_slices / verify_slice_proofs call."""
-    size = _lib.lib().chipa_audit_scratch_len(nstreams, nreq)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(_lib.lib().chipa_audit_scratch_len(nstreams, nreq), device)
 
 
 def extract_slices(streams: torch.Tensor, in_off, in_len, req_stream, index, count, proofs: torch.Tensor,
@@ -391,18 +377,12 @@ def extract_slices(streams: torch.Tensor, in_off, in_len, req_stream, index, cou
     proofs[proof_off[r] : proof_off[r] + proof_len[r]], the offsets and exact
     lengths as slice_layout gives them.  No hashing, no status.  The per-stream
     and per-request numbers are host sequences or numpy arrays."""
-    assert streams.is_cuda and proofs.is_cuda and scratch.is_cuda
-    assert streams.dtype == proofs.dtype == torch.uint8 and streams.dim() == proofs.dim() == 1
-    assert streams.is_contiguous() and proofs.is_contiguous()
-    ioff, pioff, nstreams = _arr(in_off)
-    ilen, pilen, nl = _arr(in_len)
-    rs, prs, nreq = _arr(req_stream, np.uint32)
-    idx, pidx, ni = _arr(index)
-    cnt, pcnt, nc = _arr(count)
-    poff, ppoff, npo = _arr(proof_off)
-    plen, pplen, npl = _arr(proof_len)
-    assert nl == nstreams and ni == nreq == nc == npo == npl
-    assert _fits(ioff, ilen[:nstreams], streams.numel()) and _fits(poff, plen[:nreq], proofs.numel())
+    _flat(streams, proofs)
+    _resident(scratch)
+    (ioff, ilen), (pioff, pilen), nstreams = _cols("QQ", in_off, in_len)
+    (rs, idx, cnt, poff, plen), (prs, pidx, pcnt, ppoff, pplen), nreq = _cols("IQQQQ", req_stream, index, count,
+                                                                              proof_off, proof_len)
+    assert _fits(ioff, ilen, streams.numel()) and _fits(poff, plen, proofs.numel())
     assert scratch.numel() >= _lib.lib().chipa_audit_scratch_len(nstreams, nreq)
     check(_lib.lib().chipa_extract_slices_dev(_p(streams), pioff, pilen, nstreams, prs, pidx, pcnt, nreq, _p(proofs),
                                               ppoff, pplen, _p(scratch), _stream()))
@@ -416,26 +396,20 @@ def verify_slices(streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, r
     hash) disagrees.  content[content_off[r] :] receives the request's content
     where the status is 0 and zeros otherwise (offsets as slice_layout gives
     them).  Returns the content length per request."""
-    assert streams.is_cuda and content.is_cuda and hashes.is_cuda and status.is_cuda and scratch.is_cuda
-    assert streams.dtype == content.dtype == torch.uint8 and streams.dim() == content.dim() == 1
-    assert streams.is_contiguous() and content.is_contiguous() and hashes.is_contiguous()
-    ioff, pioff, nstreams = _arr(in_off)
-    ilen, pilen, nl = _arr(in_len)
-    rs, prs, nreq = _arr(req_stream, np.uint32)
-    idx, pidx, ni = _arr(index)
-    cnt, pcnt, nc = _arr(count)
-    coff, pcoff, nco = _arr(content_off)
-    assert nl == nstreams and ni == nreq == nc == nco
-    assert hashes.numel() >= 32 * nstreams and status.numel() >= nreq and status.element_size() == 4
-    assert _fits(ioff, ilen[:nstreams], streams.numel())
+    _flat(streams, content)
+    _resident(scratch)
+    (ioff, ilen), (pioff, pilen), nstreams = _cols("QQ", in_off, in_len)
+    (rs, idx, cnt, coff), (prs, pidx, pcnt, pcoff), nreq = _cols("IQQQ", req_stream, index, count, content_off)
+    _hashes(hashes, nstreams)
+    _words(nreq, status, contiguous=False)
+    assert _fits(ioff, ilen, streams.numel())
     assert scratch.numel() >= _lib.lib().chipa_audit_scratch_len(nstreams, nreq)
-    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
     if nreq and int(rs.max()) < nstreams:  # the content buffer is checked before the call (else: the call reports it)
-        assert _fits(coff, _content_lens(_stream_content_lens(ilen)[rs[:nreq]], idx[:nreq], cnt[:nreq]), content.numel())
+        assert _fits(coff, _content_lens(_stream_content_lens(ilen)[rs], idx, cnt), content.numel())
+    clen, pclen = _out(nreq)
     check(_lib.lib().chipa_verify_slices_dev(_p(streams), pioff, pilen, _p(hashes), nstreams, prs, pidx, pcnt, nreq,
-                                             _p(content), pcoff, clen.ctypes.data_as(_lib.c_u64p), _p(status),
-                                             _p(scratch), _stream()))
-    return clen[:nreq].tolist()
+                                             _p(content), pcoff, pclen, _p(status), _p(scratch), _stream()))
+    return clen.tolist()
 
 
 def verify_slice_proofs(proofs: torch.Tensor, proof_off, proof_len, content_lens, hashes: torch.Tensor, index, count,
@@ -445,25 +419,19 @@ def verify_slice_proofs(proofs: torch.Tensor, proof_off, proof_len, content_lens
     content_lens[r] the content length of the stream it came from, hashes
     uint8 [nreq, 32] that stream's hash (one per request).  status and content
     as verify_slices.  Returns the content length per request."""
-    assert proofs.is_cuda and content.is_cuda and hashes.is_cuda and status.is_cuda and scratch.is_cuda
-    assert proofs.dtype == content.dtype == torch.uint8 and proofs.dim() == content.dim() == 1
-    assert proofs.is_contiguous() and content.is_contiguous() and hashes.is_contiguous()
-    poff, ppoff, nreq = _arr(proof_off)
-    plen, pplen, npl = _arr(proof_len)
-    n, pn, nn = _arr(content_lens)
-    idx, pidx, ni = _arr(index)
-    cnt, pcnt, nc = _arr(count)
-    coff, pcoff, nco = _arr(content_off)
-    assert npl == nreq == nn == ni == nc == nco
-    assert hashes.numel() >= 32 * nreq and status.numel() >= nreq and status.element_size() == 4
-    assert _fits(poff, plen[:nreq], proofs.numel())
+    _flat(proofs, content)
+    _resident(scratch)
+    (poff, plen, n, idx, cnt, coff), (ppoff, pplen, pn, pidx, pcnt, pcoff), nreq = _cols(
+        "QQQQQQ", proof_off, proof_len, content_lens, index, count, content_off)
+    _hashes(hashes, nreq)
+    _words(nreq, status, contiguous=False)
+    assert _fits(poff, plen, proofs.numel())
     assert scratch.numel() >= _lib.lib().chipa_audit_scratch_len(nreq, nreq)
-    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
-    assert _fits(coff, _content_lens(n[:nreq], idx[:nreq], cnt[:nreq]), content.numel())  # before the call
+    assert _fits(coff, _content_lens(n, idx, cnt), content.numel())  # before the call
+    clen, pclen = _out(nreq)
     check(_lib.lib().chipa_verify_proofs_dev(_p(proofs), ppoff, pplen, pn, _p(hashes), pidx, pcnt, nreq, _p(content),
-                                             pcoff, clen.ctypes.data_as(_lib.c_u64p), _p(status), _p(scratch),
-                                             _stream()))
-    return clen[:nreq].tolist()
+                                             pcoff, pclen, _p(status), _p(scratch), _stream()))
+    return clen.tolist()
 
 
 # ---- ragged scrub (include/carbonado_hip_repair.h): shard verdicts and repair
@@ -477,7 +445,7 @@ def scrub_ragged_scratch(in_len, nrepair=None, device=None) -> torch.Tensor:
     them, one pass; 1: the least a call accepts)."""
     ln, pl, count = _arr(in_len)
     size = _lib.lib().chipr_scrub_ragged_scratch_len(pl, count, count if nrepair is None else int(nrepair))
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(size, device)
 
 
 def shard_masks_ragged(enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, chunk_len,
@@ -487,16 +455,14 @@ def shard_masks_ragged(enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, 
     verifies against hashes[o] (uint8 [count, 32]); 255 = intact, 0 also for a
     damaged header or a chunk_len that does not fit the stream.  Enqueued on
     the current stream, not synchronised."""
-    assert enc.is_cuda and hashes.is_cuda and scratch.is_cuda
-    assert enc.dtype == torch.uint8 and enc.dim() == 1 and enc.is_contiguous() and hashes.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ilen, pilen, nl = _arr(in_len)
-    cl, pcl, ncl = _arr(chunk_len, np.uint32)
-    assert nl == count == ncl and hashes.numel() >= 32 * count
-    assert _fits(ioff, ilen[:count], enc.numel())
+    _flat(enc)
+    _resident(scratch)
+    (ioff, ilen, cl), (pioff, pilen, pcl), count = _cols("QQI", in_off, in_len, chunk_len)
+    _hashes(hashes, count)
+    assert _fits(ioff, ilen, enc.numel())
     if masks is None:
         masks = torch.empty(count, dtype=torch.int32, device=enc.device)
-    assert masks.is_cuda and masks.numel() >= count and masks.element_size() == 4 and masks.is_contiguous()
+    _words(count, masks)
     check(_lib.lib().chipr_shard_masks_ragged_dev(_p(enc), pioff, pilen, count, _p(hashes), pcl, _p(masks), _p(scratch),
                                                   scratch.numel(), _stream()))
     return masks
@@ -517,49 +483,43 @@ def scrub_ragged(enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, paddin
     in_off[o]: the stream is repaired where it lies.  The repairs run in as
     many passes as `scratch` requires (scrub_ragged_scratch); the results do
     not depend on it.  Synchronous."""
-    assert enc.is_cuda and out.is_cuda and hashes.is_cuda and scratch.is_cuda
-    assert enc.dtype == out.dtype == torch.uint8 and enc.dim() == out.dim() == 1
-    assert enc.is_contiguous() and out.is_contiguous() and hashes.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ilen, pilen, nl = _arr(in_len)
-    ooff, pooff, no = _arr(out_off)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    cl, pcl, ncl = _arr(chunk_len, np.uint32)
-    assert nl == count == no == npad == ncl and hashes.numel() >= 32 * count
-    assert _fits(ioff, ilen[:count], enc.numel()) and _fits(ooff, ilen[:count], out.numel())
-    status = np.zeros(max(count, 1), dtype=np.int32)
+    _flat(enc, out)
+    _resident(scratch)
+    (ioff, ilen, ooff, pad, cl), (pioff, pilen, pooff, ppad, pcl), count = _ragged(
+        enc, in_off, in_len, out, out_off, padding, chunk_len, kinds="II")
+    _hashes(hashes, count)
+    status, pstatus = _out(count, np.int32)
     check(_lib.lib().chipr_scrub_ragged_dev(_p(enc), pioff, pilen, count, _p(hashes), ppad, pcl, _p(out), pooff,
-                                            status.ctypes.data_as(ctypes.c_void_p), _p(scratch), scratch.numel(),
-                                            _stream()))
-    return status[:count]
+                                            pstatus, _p(scratch), scratch.numel(), _stream()))
+    return status
 
 
 # ---- ranged reads (include/carbonado_hip_read.h): byte ranges of resident
 # Zfec|Bao objects, rebuilt from other shards where the primary's chunks are
 # damaged.  A request r is (req_stream[r], start[r], len[r]) in object bytes
 
+def _read_layout(layout, chunk_len, padding, req_stream, start, length, align):
+    """read_layout and plain_read_layout: `layout` is the header's call"""
+    (cl, pad), (pcl, ppad), nstreams = _cols("II", chunk_len, padding)
+    (rs, st, ln), (prs, pst, pln), nreq = _cols("IQQ", req_stream, start, length)
+    (off, poff), (clen, pclen) = _out(nreq), _out(nreq)
+    total, nseg = ctypes.c_uint64(), ctypes.c_uint64()
+    check(layout(pcl, ppad, nstreams, prs, pst, pln, nreq, align, poff, pclen, ctypes.byref(total), ctypes.byref(nseg)))
+    return off.tolist(), clen.tolist(), total.value, nseg.value
+
+
 def read_layout(chunk_len, padding, req_stream, start, length, align: int = 16):
     """Where read_ranges' caller should put every request's content (host
     only).  Returns (content_off, content_len, content_total, nseg): offsets
     into one content buffer, each range on a multiple of `align` (a multiple of
     16), and the segments of the call for read_scratch."""
-    cl, pcl, nstreams = _arr(chunk_len, np.uint32)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    rs, prs, nreq = _arr(req_stream, np.uint32)
-    st, pst, ns = _arr(start)
-    ln, pln, nl = _arr(length)
-    assert npad == nstreams and ns == nreq == nl
-    off, clen = np.zeros(max(nreq, 1), dtype=np.uint64), np.zeros(max(nreq, 1), dtype=np.uint64)
-    total, nseg = ctypes.c_uint64(), ctypes.c_uint64()
-    check(_lib.lib().chipd_read_layout(pcl, ppad, nstreams, prs, pst, pln, nreq, align, off.ctypes.data_as(_lib.c_u64p),
-                                       clen.ctypes.data_as(_lib.c_u64p), ctypes.byref(total), ctypes.byref(nseg)))
-    return off[:nreq].tolist(), clen[:nreq].tolist(), total.value, nseg.value
+    return _read_layout(lambda *args: _lib.lib().chipd_read_layout(*args), chunk_len, padding, req_stream, start, length,
+                        align)
 
 
 def read_scratch(nreq: int, nseg: int, device=None) -> torch.Tensor:
     """Scratch of a read_ranges call of nreq requests in nseg segments (read_layout)."""
-    size = _lib.lib().chipd_read_scratch_len(nreq, nseg)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(_lib.lib().chipd_read_scratch_len(nreq, nseg), device)
 
 
 def read_ranges(streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len, req_stream, start,
@@ -575,29 +535,16 @@ def read_ranges(streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, pad
     used [nreq]: the shards each request was served from (bit p alone: copied
     from primary p).  Enqueued on the current stream, not synchronised.
     Returns the content length per request."""
-    assert streams.is_cuda and content.is_cuda and hashes.is_cuda and status.is_cuda and used.is_cuda and scratch.is_cuda
-    assert streams.dtype == content.dtype == torch.uint8 and streams.dim() == content.dim() == 1
-    assert streams.is_contiguous() and content.is_contiguous() and hashes.is_contiguous()
-    ioff, pioff, nstreams = _arr(in_off)
-    ilen, pilen, nl = _arr(in_len)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    cl, pcl, ncl = _arr(chunk_len, np.uint32)
-    rs, prs, nreq = _arr(req_stream, np.uint32)
-    st, pst, ns = _arr(start)
-    ln, pln, nln = _arr(length)
-    coff, pcoff, nco = _arr(content_off)
-    assert nl == nstreams == npad == ncl and ns == nreq == nln == nco
-    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
-    for t in (status, used):
-        assert t.numel() >= nreq and t.element_size() == 4 and t.is_contiguous()
-    if nreq and int(rs.max()) < nstreams:  # the content buffer is checked before the call (else: the call reports it)
-        _, want, _, _ = read_layout(cl[:nstreams], pad[:nstreams], rs[:nreq], st[:nreq], ln[:nreq])
-        assert _fits(coff, np.asarray(want, dtype=np.uint64), content.numel())
-    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
+    (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
+                                                                              chunk_len)
+    _resident(scratch)
+    (rs, st, ln, coff, clen), (prs, pst, pln, pcoff, pclen), nreq = _request_args(
+        req_stream, start, length, content_off, content, (status, used), nstreams,
+        lambda *req: read_layout(cl, pad, *req)[1])
     check(_lib.lib().chipd_read_ranges_dev(_p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams, prs, pst, pln,
-                                           nreq, _p(content), pcoff, clen.ctypes.data_as(_lib.c_u64p), _p(status),
-                                           _p(used), _p(scratch), scratch.numel(), _stream()))
-    return clen[:nreq].tolist()
+                                           nreq, _p(content), pcoff, pclen, _p(status), _p(used), _p(scratch),
+                                           scratch.numel(), _stream()))
+    return clen.tolist()
 
 
 # ---- vouched ranged reads (include/carbonado_hip_vread.h): read_ranges with
@@ -609,8 +556,7 @@ VREAD_STRICT = 1                            # flag: a request with an unvouched 
 
 def vread_scratch(nreq: int, nseg: int, device=None) -> torch.Tensor:
     """Scratch of a read_ranges_vouched call of nreq requests in nseg segments (read_layout)."""
-    size = _lib.lib().chipv_read_scratch_len(nreq, nseg)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(_lib.lib().chipv_read_scratch_len(nreq, nseg), device)
 
 
 def read_ranges_vouched(streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len, req_stream,
@@ -629,30 +575,16 @@ def read_ranges_vouched(streams: torch.Tensor, in_off, in_len, hashes: torch.Ten
     status 0 and no UNVOUCHED bit every byte is hashed against the root.
     status, used and vouch are filled on the device; enqueued on the current
     stream, not synchronised.  Returns the content length per request."""
-    assert streams.is_cuda and content.is_cuda and hashes.is_cuda and status.is_cuda and used.is_cuda and scratch.is_cuda
-    assert vouch.is_cuda
-    assert streams.dtype == content.dtype == torch.uint8 and streams.dim() == content.dim() == 1
-    assert streams.is_contiguous() and content.is_contiguous() and hashes.is_contiguous()
-    ioff, pioff, nstreams = _arr(in_off)
-    ilen, pilen, nl = _arr(in_len)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    cl, pcl, ncl = _arr(chunk_len, np.uint32)
-    rs, prs, nreq = _arr(req_stream, np.uint32)
-    st, pst, ns = _arr(start)
-    ln, pln, nln = _arr(length)
-    coff, pcoff, nco = _arr(content_off)
-    assert nl == nstreams == npad == ncl and ns == nreq == nln == nco
-    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
-    for t in (status, used, vouch):
-        assert t.numel() >= nreq and t.element_size() == 4 and t.is_contiguous()
-    if nreq and int(rs.max()) < nstreams:  # the content buffer is checked before the call (else: the call reports it)
-        _, want, _, _ = read_layout(cl[:nstreams], pad[:nstreams], rs[:nreq], st[:nreq], ln[:nreq])
-        assert _fits(coff, np.asarray(want, dtype=np.uint64), content.numel())
-    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
+    (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
+                                                                              chunk_len)
+    _resident(scratch)
+    (rs, st, ln, coff, clen), (prs, pst, pln, pcoff, pclen), nreq = _request_args(
+        req_stream, start, length, content_off, content, (status, used, vouch), nstreams,
+        lambda *req: read_layout(cl, pad, *req)[1])
     check(_lib.lib().chipv_read_ranges_dev(_p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams, prs, pst, pln,
-                                           nreq, _p(content), pcoff, clen.ctypes.data_as(_lib.c_u64p), _p(status),
-                                           _p(used), _p(vouch), flags, _p(scratch), scratch.numel(), _stream()))
-    return clen[:nreq].tolist()
+                                           nreq, _p(content), pcoff, pclen, _p(status), _p(used), _p(vouch), flags,
+                                           _p(scratch), scratch.numel(), _stream()))
+    return clen.tolist()
 
 
 # ---- ranged reads planned on the device (include/carbonado_hip_qread.h): the
@@ -676,14 +608,8 @@ def stream_table(streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, pa
     current stream.  The table serves every later read_ranges_planned call
     while the streams and hashes stay where they are; an in-place scrub does not
     invalidate it."""
-    assert streams.is_cuda and hashes.is_cuda and streams.dtype == torch.uint8 and streams.dim() == 1
-    assert streams.is_contiguous() and hashes.is_contiguous()
-    ioff, pioff, nstreams = _arr(in_off)
-    ilen, pilen, nl = _arr(in_len)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    cl, pcl, ncl = _arr(chunk_len, np.uint32)
-    assert nl == nstreams == npad == ncl
-    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
+    (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
+                                                                              chunk_len)
     table = torch.empty(_lib.lib().chipq_stream_table_len(nstreams), dtype=torch.uint8, device=streams.device)
     info = _lib.TableInfo()
     check(_lib.lib().chipq_stream_table_dev(_p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams, _p(table),
@@ -698,7 +624,7 @@ def planned_read_scratch(table: StreamTable, nreq: int, max_len: int, vouched: b
     size = _lib.lib().chipq_read_scratch_len(ctypes.byref(table.info), nreq, max_len, 1 if vouched else 0)
     if nreq and not size:
         raise ValueError("the call would refuse this capacity")
-    return torch.empty(size, dtype=torch.uint8, device=device or table.table.device)
+    return _scratch(size, device or table.table.device)
 
 
 def _planned_args(table, req_stream, start, length, max_len, content, content_stride, content_len, words, scratch):
@@ -706,10 +632,9 @@ def _planned_args(table, req_stream, start, length, max_len, content, content_st
     assert start.numel() == length.numel() == content_len.numel() == nreq
     assert req_stream.element_size() == 4 and start.element_size() == length.element_size() == 8
     assert content_len.element_size() == 8 and content.dtype == torch.uint8 and content.dim() == 1
-    for t in (req_stream, start, length, content, content_len, scratch, table.table) + tuple(words):
+    for t in (req_stream, start, length, content, content_len, scratch, table.table):
         assert t.is_cuda and t.is_contiguous()
-    for t in words:
-        assert t.numel() >= nreq and t.element_size() == 4
+    _words(nreq, *words)
     assert nreq == 0 or content.numel() >= (nreq - 1) * content_stride + min(content_stride, (max_len + 15) // 16 * 16)
     return nreq
 
@@ -758,18 +683,7 @@ ECIES_FAILED = 17  # status of a message whose tag does not verify (CHIP_ERR_ECI
 def gcm_scratch(n, device=None) -> torch.Tensor:
     """Scratch of a gcm_seal_ragged / gcm_open_ragged call over messages of n[o] bytes."""
     ln, pln, count = _arr(n)
-    size = _lib.lib().chipe_gcm_scratch_len(pln, count)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
-
-
-def _gcm_keys(keys, ivs, count):
-    k = np.frombuffer(bytes(keys), dtype=np.uint8) if not isinstance(keys, np.ndarray) else keys
-    v = np.frombuffer(bytes(ivs), dtype=np.uint8) if not isinstance(ivs, np.ndarray) else ivs
-    k, v = np.ascontiguousarray(k, dtype=np.uint8).reshape(-1), np.ascontiguousarray(v, dtype=np.uint8).reshape(-1)
-    assert k.size == 32 * count and v.size == 16 * count
-    keep_k = k if k.size else np.zeros(1, dtype=np.uint8)
-    keep_v = v if v.size else np.zeros(1, dtype=np.uint8)
-    return keep_k, keep_k.ctypes.data_as(_lib.c_u8p), keep_v, keep_v.ctypes.data_as(_lib.c_u8p)
+    return _scratch(_lib.lib().chipe_gcm_scratch_len(pln, count), device)
 
 
 def gcm_seal_ragged(keys, ivs, inp: torch.Tensor, in_off, n, out: torch.Tensor, out_off, tags: torch.Tensor,
@@ -781,14 +695,11 @@ def gcm_seal_ragged(keys, ivs, inp: torch.Tensor, in_off, n, out: torch.Tensor, 
     table-free GHASH on the device; the key region of the scratch is zeroed by
     the call's last operation.  Enqueued on the current stream, not
     synchronised."""
-    assert inp.is_cuda and out.is_cuda and tags.is_cuda and scratch.is_cuda
-    assert inp.dtype == out.dtype == tags.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ln, pln, nl = _arr(n)
-    ooff, pooff, no = _arr(out_off)
-    assert nl == count == no and tags.numel() >= 16 * count and tags.is_contiguous()
-    assert _fits(ioff, ln[:count], inp.numel()) and _fits(ooff, ln[:count], out.numel())
-    kk, pk, vv, pv = _gcm_keys(keys, ivs, count)
+    _flat(inp, out, tags, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff), (pioff, pln, pooff), count = _ragged(inp, in_off, n, out, out_off)
+    assert tags.numel() >= 16 * count
+    kv, (pk, pv), _ = _gcm_keys(keys, ivs, count)
     check(_lib.lib().chipe_gcm_seal_ragged_dev(pk, pv, _p(inp), pioff, pln, count, _p(out), pooff, _p(tags),
                                                _p(scratch), scratch.numel(), _stream()))
 
@@ -802,15 +713,12 @@ def gcm_open_ragged(keys, ivs, inp: torch.Tensor, in_off, n, tags: torch.Tensor,
     status[o] = ECIES_FAILED and zeros over its whole range, the others 0 and
     their plaintext.  status int32 / uint32 [count] on the device.  Enqueued on
     the current stream, not synchronised."""
-    assert inp.is_cuda and out.is_cuda and tags.is_cuda and scratch.is_cuda and status.is_cuda
-    assert inp.dtype == out.dtype == tags.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ln, pln, nl = _arr(n)
-    ooff, pooff, no = _arr(out_off)
-    assert nl == count == no and tags.numel() >= 16 * count and tags.is_contiguous()
-    assert status.numel() >= count and status.element_size() == 4 and status.is_contiguous()
-    assert _fits(ioff, ln[:count], inp.numel()) and _fits(ooff, ln[:count], out.numel())
-    kk, pk, vv, pv = _gcm_keys(keys, ivs, count)
+    _flat(inp, out, tags, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff), (pioff, pln, pooff), count = _ragged(inp, in_off, n, out, out_off)
+    assert tags.numel() >= 16 * count
+    _words(count, status)
+    kv, (pk, pv), _ = _gcm_keys(keys, ivs, count)
     check(_lib.lib().chipe_gcm_open_ragged_dev(pk, pv, _p(inp), pioff, pln, count, _p(tags), _p(out), pooff,
                                                _p(status), _p(scratch), scratch.numel(), _stream()))
 
@@ -825,13 +733,10 @@ def ecies_seal_ragged(pubkey: bytes, inp: torch.Tensor, in_off, n, out: torch.Te
     None, or a list of (ephemeral_sk 32 B, nonce 16 B) per object for bit-exact
     tests.  scratch: gcm_scratch(n).  Enqueued on the current stream, not
     synchronised."""
-    assert inp.is_cuda and out.is_cuda and scratch.is_cuda and inp.dtype == out.dtype == torch.uint8
-    assert inp.is_contiguous() and out.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ln, pln, nl = _arr(n)
-    ooff, pooff, no = _arr(out_off)
-    assert nl == count == no
-    assert _fits(ioff, ln[:count], inp.numel()) and _fits(ooff, ln[:count] + np.uint64(97), out.numel())
+    _flat(inp, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff), (pioff, pln, pooff), count = _ragged(inp, in_off, n, out, out_off,
+                                                           room=lambda ln: ln + np.uint64(97))
     assert scratch.numel() >= _lib.lib().chipe_gcm_scratch_len(pln, count)
     inj, keep = _inject_array(inject, count)
     check(_lib.lib().chipe_seal_ragged_dev(bytes(pubkey), len(pubkey), inj, _p(inp), pioff, pln, count, _p(out), pooff,
@@ -848,21 +753,21 @@ def ecies_open_ragged(secret_key: bytes, inp: torch.Tensor, in_off, in_len, out:
     keys depend on them); the rest is enqueued on the current stream.  scratch:
     gcm_scratch of the plaintext lengths.  Returns the plaintext length per
     object."""
-    assert inp.is_cuda and out.is_cuda and scratch.is_cuda and status.is_cuda
-    assert inp.dtype == out.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ln, pln, nl = _arr(in_len)
-    ooff, pooff, no = _arr(out_off)
-    assert nl == count == no and _fits(ioff, ln[:count], inp.numel())
-    assert status.numel() >= count and status.element_size() == 4 and status.is_contiguous()
-    plain = np.where(ln[:count] >= 97, ln[:count] - np.uint64(97), np.uint64(0)).astype(np.uint64)
-    assert _fits(ooff, plain, out.numel())
-    pl, ppl, _ = _arr(plain)
+    _flat(inp, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff), (pioff, pln, pooff), count = _ragged(inp, in_off, in_len, out, out_off, room=_plain_lens)
+    _words(count, status)
+    pl, ppl, _ = _arr(_plain_lens(ln))
     assert scratch.numel() >= _lib.lib().chipe_gcm_scratch_len(ppl, count)
-    olen = np.zeros(max(count, 1), dtype=np.uint64)
+    olen, polen = _out(count)
     check(_lib.lib().chipe_open_ragged_dev(bytes(secret_key), len(secret_key), _p(inp), pioff, pln, count, _p(out),
-                                           pooff, olen.ctypes.data_as(_lib.c_u64p), _p(status), _p(scratch), _stream()))
-    return olen[:count].tolist()
+                                           pooff, polen, _p(status), _p(scratch), _stream()))
+    return olen.tolist()
+
+
+def _plain_lens(ln):
+    """plaintext bytes of envelopes of ln bytes (eph_pub65 || nonce16 || tag16 come off)"""
+    return np.where(ln >= 97, ln - np.uint64(97), np.uint64(0)).astype(np.uint64)
 
 
 def _inject_array(inject, count):
@@ -881,7 +786,7 @@ def ecies_ragged_scratch(fmt: int, lens, decode: bool = False, device=None) -> t
     """Scratch of encode_ragged_ecies (object lengths) / decode_ragged_ecies (stream lengths)."""
     ln, pln, count = _arr(lens)
     fn = _lib.lib().chipe_decode_scratch_len if decode else _lib.lib().chipe_encode_scratch_len
-    return torch.empty(fn(fmt, pln, count), dtype=torch.uint8, device=device or "cuda")
+    return _scratch(fn(fmt, pln, count), device)
 
 
 def encode_ragged_ecies(fmt: int, pubkey: bytes, inp: torch.Tensor, in_off, sizes, out: torch.Tensor, out_off,
@@ -891,22 +796,16 @@ def encode_ragged_ecies(fmt: int, pubkey: bytes, inp: torch.Tensor, in_off, size
     encode_ragged does at fmt & 12 (offsets: ragged_layout(fmt & 12, sizes +
     97)).  Stream bytes, hash and EncodeInfo are those of encode() at fmt.
     Returns (encoded length per object, EncodeInfo per object)."""
-    from .structs import EncodeInfo
-    assert inp.is_cuda and out.is_cuda and hashes.is_cuda and scratch.is_cuda
-    assert inp.dtype == out.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ln, pln, nl = _arr(sizes)
-    ooff, pooff, no = _arr(out_off)
-    assert nl == count == no and hashes.numel() >= 32 * count and hashes.is_contiguous()
-    assert _fits(ioff, ln[:count], inp.numel())
+    _flat(inp, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff), (pioff, pln, pooff), count = _ragged(inp, in_off, sizes, out, out_off, room=None)
+    _hashes(hashes, count)
     assert scratch.numel() >= _lib.lib().chipe_encode_scratch_len(fmt, pln, count)
     inj, keep = _inject_array(inject, count)
-    olen = (ctypes.c_uint64 * max(count, 1))()
-    info = (_lib.EncodeInfoC * max(count, 1))()
+    olen, polen, info = _encode_outputs(count)
     check(_lib.lib().chipe_encode_ragged_dev(fmt, bytes(pubkey), len(pubkey), inj, _p(inp), pioff, pln, count, _p(out),
-                                             pooff, olen, _p(hashes), info, _p(scratch), _stream()))
-    assert all(int(a) + b <= out.numel() for a, b in zip(ooff[:count], list(olen)[:count]))
-    return list(olen)[:count], [EncodeInfo.from_c(info[o]) for o in range(count)]
+                                             pooff, polen, _p(hashes), info, _p(scratch), _stream()))
+    return _encoded(olen, info, ooff, out)
 
 
 def decode_ragged_ecies(fmt: int, secret_key: bytes, enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding,
@@ -915,21 +814,18 @@ def decode_ragged_ecies(fmt: int, secret_key: bytes, enc: torch.Tensor, in_off, 
     fmt & 12 into envelopes in the scratch, then ecies_open_ragged.  status[o]:
     0, the bao status of a damaged stream (not opened, zeros), or ECIES_FAILED.
     Returns the plaintext length per object."""
-    assert enc.is_cuda and out.is_cuda and status.is_cuda and scratch.is_cuda
-    assert enc.dtype == out.dtype == torch.uint8 and enc.is_contiguous() and out.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ln, pln, nl = _arr(in_len)
-    ooff, pooff, no = _arr(out_off)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    assert nl == count == no == npad and _fits(ioff, ln[:count], enc.numel())
-    assert status.numel() >= count and status.element_size() == 4 and status.is_contiguous()
+    _flat(enc, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff, pad), (pioff, pln, pooff, ppad), count = _ragged(enc, in_off, in_len, out, out_off, padding,
+                                                                      kinds="I", room=None)
+    _words(count, status)
     assert scratch.numel() >= _lib.lib().chipe_decode_scratch_len(fmt, pln, count)
-    olen = np.zeros(max(count, 1), dtype=np.uint64)
+    olen, polen = _out(count)
     check(_lib.lib().chipe_decode_ragged_dev(fmt, bytes(secret_key), len(secret_key), _p(enc), pioff, pln, count,
                                              _p(hashes) if hashes is not None else None, ppad, _p(out), pooff,
-                                             olen.ctypes.data_as(_lib.c_u64p), _p(status), _p(scratch), _stream()))
-    assert _fits(ooff, olen[:count], out.numel())
-    return olen[:count].tolist()
+                                             polen, _p(status), _p(scratch), _stream()))
+    assert _fits(ooff, olen, out.numel())
+    return olen.tolist()
 
 
 # ---- plaintext ranged reads of level-13 streams (include/carbonado_hip_cread.h):
@@ -937,8 +833,7 @@ def decode_ragged_ecies(fmt: int, secret_key: bytes, enc: torch.Tensor, in_off, 
 
 def ctr_scratch(nkeys: int, nitems: int, device=None) -> torch.Tensor:
     """Scratch of a ctr_ranges call over nitems items under nkeys keys."""
-    size = _lib.lib().chipc_ctr_scratch_len(nkeys, nitems)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(_lib.lib().chipc_ctr_scratch_len(nkeys, nitems), device)
 
 
 def ctr_ranges(keys, ivs, item_key, pos, n, buf: torch.Tensor, buf_off, scratch: torch.Tensor,
@@ -950,16 +845,13 @@ def ctr_ranges(keys, ivs, item_key, pos, n, buf: torch.Tensor, buf_off, scratch:
     uint32 [nitems] on the device: item i is skipped where gate[i] != 0.  The
     key region of the scratch is zeroed by the call's last operation.  Enqueued
     on the current stream, not synchronised."""
-    assert buf.is_cuda and scratch.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous()
-    ik, pik, nitems = _arr(item_key, np.uint32)
-    ps, pps, npos = _arr(pos)
-    ln, pln, nl = _arr(n)
-    off, poff, no = _arr(buf_off)
-    assert npos == nitems == nl == no and _fits(off, ln[:nitems], buf.numel())
-    nkeys = len(bytes(keys)) // 32 if not isinstance(keys, np.ndarray) else keys.size // 32
-    kk, pk, vv, pv = _gcm_keys(keys, ivs, nkeys)
+    _flat(buf, one_dim=False)
+    _resident(scratch)
+    (ik, ps, ln, off), (pik, pps, pln, poff), nitems = _cols("IQQQ", item_key, pos, n, buf_off)
+    assert _fits(off, ln, buf.numel())
+    kv, (pk, pv), nkeys = _gcm_keys(keys, ivs)
     if gate is not None:
-        assert gate.is_cuda and gate.numel() >= nitems and gate.element_size() == 4 and gate.is_contiguous()
+        _words(nitems, gate)
     check(_lib.lib().chipc_ctr_ranges_dev(pk, pv, nkeys, pik, pps, pln, nitems, _p(buf), poff,
                                           _p(gate) if gate is not None else None, _p(scratch), scratch.numel(),
                                           _stream()))
@@ -967,8 +859,7 @@ def ctr_ranges(keys, ivs, item_key, pos, n, buf: torch.Tensor, buf_off, scratch:
 
 def stream_keys_scratch(nstreams: int, device=None) -> torch.Tensor:
     """Scratch of a stream_keys call over nstreams streams."""
-    size = _lib.lib().chipc_stream_keys_scratch_len(nstreams)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(_lib.lib().chipc_stream_keys_scratch_len(nstreams), device)
 
 
 def stream_keys(secret_key: bytes, streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len,
@@ -981,45 +872,28 @@ def stream_keys(secret_key: bytes, streams: torch.Tensor, in_off, in_len, hashes
     or 7 for a header that cannot be served, ECIES_FAILED for an object shorter
     than 97 bytes or an ephemeral key that does not parse (key and nonce are
     zeros then).  The keys are the caller's to hold and wipe."""
-    assert streams.is_cuda and hashes.is_cuda and scratch.is_cuda and streams.dtype == torch.uint8
-    assert streams.is_contiguous() and hashes.is_contiguous()
-    ioff, pioff, nstreams = _arr(in_off)
-    ilen, pilen, nl = _arr(in_len)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    cl, pcl, ncl = _arr(chunk_len, np.uint32)
-    assert nl == nstreams == npad == ncl
-    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
-    keys = np.zeros((max(nstreams, 1), 32), dtype=np.uint8)
-    ivs = np.zeros((max(nstreams, 1), 16), dtype=np.uint8)
-    status = np.zeros(max(nstreams, 1), dtype=np.uint32)
+    (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
+                                                                              chunk_len)
+    _resident(scratch)
+    (keys, pkeys), (ivs, pivs) = _out(nstreams, np.uint8, 32), _out(nstreams, np.uint8, 16)
+    status, pstatus = _out(nstreams, np.uint32)
     check(_lib.lib().chipc_stream_keys_dev(bytes(secret_key), len(secret_key), _p(streams), pioff, pilen, _p(hashes),
-                                           ppad, pcl, nstreams, keys.ctypes.data_as(_lib.c_u8p),
-                                           ivs.ctypes.data_as(_lib.c_u8p), status.ctypes.data_as(_lib.c_u32p),
-                                           _p(scratch), scratch.numel(), _stream()))
-    return keys[:nstreams], ivs[:nstreams], status[:nstreams]
+                                           ppad, pcl, nstreams, pkeys, pivs, pstatus, _p(scratch), scratch.numel(),
+                                           _stream()))
+    return keys, ivs, status
 
 
 def plain_read_layout(chunk_len, padding, req_stream, start, length, align: int = 16):
     """read_layout for requests in plaintext bytes of level-13 streams: (content_off,
     content_len, content_total, nseg) of plaintext [start, min(P, start +
     length)), P = 4 chunk_len - padding - 97."""
-    cl, pcl, nstreams = _arr(chunk_len, np.uint32)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    rs, prs, nreq = _arr(req_stream, np.uint32)
-    st, pst, ns = _arr(start)
-    ln, pln, nl = _arr(length)
-    assert npad == nstreams and ns == nreq == nl
-    off, clen = np.zeros(max(nreq, 1), dtype=np.uint64), np.zeros(max(nreq, 1), dtype=np.uint64)
-    total, nseg = ctypes.c_uint64(), ctypes.c_uint64()
-    check(_lib.lib().chipc_read_layout(pcl, ppad, nstreams, prs, pst, pln, nreq, align, off.ctypes.data_as(_lib.c_u64p),
-                                       clen.ctypes.data_as(_lib.c_u64p), ctypes.byref(total), ctypes.byref(nseg)))
-    return off[:nreq].tolist(), clen[:nreq].tolist(), total.value, nseg.value
+    return _read_layout(lambda *args: _lib.lib().chipc_read_layout(*args), chunk_len, padding, req_stream, start, length,
+                        align)
 
 
 def plain_read_scratch(nreq: int, nseg: int, nstreams: int, device=None) -> torch.Tensor:
     """Scratch of a read_plain_ranges call of nreq requests in nseg segments (plain_read_layout)."""
-    size = _lib.lib().chipc_read_scratch_len(nreq, nseg, nstreams)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(_lib.lib().chipc_read_scratch_len(nreq, nseg, nstreams), device)
 
 
 def read_plain_ranges(keys, ivs, key_status, streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding,
@@ -1035,36 +909,18 @@ def read_plain_ranges(keys, ivs, key_status, streams: torch.Tensor, in_off, in_l
     checked: the ciphertext is vouched for by the root hash, and a wrong key
     gives status 0 and bytes that are not the plaintext.  Enqueued on the
     current stream, not synchronised.  Returns the content length per request."""
-    assert streams.is_cuda and content.is_cuda and hashes.is_cuda and status.is_cuda and used.is_cuda and scratch.is_cuda
-    assert vouch.is_cuda
-    assert streams.dtype == content.dtype == torch.uint8 and streams.dim() == content.dim() == 1
-    assert streams.is_contiguous() and content.is_contiguous() and hashes.is_contiguous()
-    ioff, pioff, nstreams = _arr(in_off)
-    ilen, pilen, nl = _arr(in_len)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    cl, pcl, ncl = _arr(chunk_len, np.uint32)
-    rs, prs, nreq = _arr(req_stream, np.uint32)
-    st, pst, ns = _arr(start)
-    ln, pln, nln = _arr(length)
-    coff, pcoff, nco = _arr(content_off)
-    assert nl == nstreams == npad == ncl and ns == nreq == nln == nco
-    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
-    for t in (status, used, vouch):
-        assert t.numel() >= nreq and t.element_size() == 4 and t.is_contiguous()
-    if nreq and int(rs.max()) < nstreams:  # the content buffer is checked before the call (else: the call reports it)
-        _, want, _, _ = plain_read_layout(cl[:nstreams], pad[:nstreams], rs[:nreq], st[:nreq], ln[:nreq])
-        assert _fits(coff, np.asarray(want, dtype=np.uint64), content.numel())
-    kk, pk, vv, pv = _gcm_keys(keys, ivs, nstreams)
-    pks = None
-    if key_status is not None:
-        ks, pks, nks = _arr(key_status, np.uint32)
-        assert nks == nstreams
-    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
+    (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
+                                                                              chunk_len)
+    _resident(scratch)
+    (rs, st, ln, coff, clen), (prs, pst, pln, pcoff, pclen), nreq = _request_args(
+        req_stream, start, length, content_off, content, (status, used, vouch), nstreams,
+        lambda *req: plain_read_layout(cl, pad, *req)[1])
+    kv, (pk, pv), _ = _gcm_keys(keys, ivs, nstreams)
+    ks, pks = _opt(key_status, nstreams)
     check(_lib.lib().chipc_read_ranges_dev(pk, pv, pks, _p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams, prs,
-                                           pst, pln, nreq, _p(content), pcoff, clen.ctypes.data_as(_lib.c_u64p),
-                                           _p(status), _p(used), _p(vouch), flags, _p(scratch), scratch.numel(),
-                                           _stream()))
-    return clen[:nreq].tolist()
+                                           pst, pln, nreq, _p(content), pcoff, pclen, _p(status), _p(used), _p(vouch),
+                                           flags, _p(scratch), scratch.numel(), _stream()))
+    return clen.tolist()
 
 
 # ---- plaintext reads of level-13 streams planned on the device
@@ -1087,14 +943,8 @@ def key_table(keys, ivs, key_status, device=None) -> KeyTable:
     The raw keys are uploaded into a staging part of the table, which is zeros
     again once the enqueued work is done.  The round keys STAY on the device, in
     the returned table, until wipe_key_table.  Enqueued on the current stream."""
-    k = np.ascontiguousarray(np.frombuffer(bytes(keys), dtype=np.uint8) if not isinstance(keys, np.ndarray) else keys,
-                             dtype=np.uint8).reshape(-1)
-    nstreams = k.size // 32
-    kk, pk, vv, pv = _gcm_keys(k, ivs, nstreams)
-    pks = None
-    if key_status is not None:
-        ks, pks, nks = _arr(key_status, np.uint32)
-        assert nks == nstreams
+    kv, (pk, pv), nstreams = _gcm_keys(keys, ivs)
+    ks, pks = _opt(key_status, nstreams)
     table = torch.empty(_lib.lib().chipk_key_table_len(nstreams), dtype=torch.uint8, device=device or "cuda")
     check(_lib.lib().chipk_key_table_dev(pk, pv, pks, nstreams, _p(table), table.numel(), _stream()))
     return KeyTable(table, nstreams)
@@ -1110,7 +960,7 @@ def planned_plain_read_scratch(table: StreamTable, nreq: int, max_len: int, devi
     size = _lib.lib().chipk_read_scratch_len(ctypes.byref(table.info), nreq, max_len)
     if nreq and not size:
         raise ValueError("the call would refuse this capacity")
-    return torch.empty(size, dtype=torch.uint8, device=device or table.table.device)
+    return _scratch(size, device or table.table.device)
 
 
 def read_plain_ranges_planned(table: StreamTable, key_table: KeyTable, req_stream: torch.Tensor, start: torch.Tensor,
@@ -1157,7 +1007,7 @@ def snap_scratch(n, out_cap=None, device=None) -> torch.Tensor:
     else:
         cap, pcap, _ = _arr(out_cap)
         size = _lib.lib().chips_unsnap_scratch_len(pln, pcap, count)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(size, device)
 
 
 def snap_ragged(inp: torch.Tensor, in_off, n, out: torch.Tensor, out_off, out_len: torch.Tensor,
@@ -1167,14 +1017,11 @@ def snap_ragged(inp: torch.Tensor, in_off, n, out: torch.Tensor, out_off, out_le
     out[out_off[o] :] at any byte offset (capacity snap_max_len(n[o])), its
     length to out_len[o] (int64 [count] on the device).  Enqueued on the
     current stream, not synchronised."""
-    assert inp.is_cuda and out.is_cuda and out_len.is_cuda and scratch.is_cuda
-    assert inp.dtype == out.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ln, pln, nl = _arr(n)
-    ooff, pooff, no = _arr(out_off)
-    assert nl == count == no and out_len.numel() >= count and out_len.element_size() == 8 and out_len.is_contiguous()
-    worst = np.array([snap_max_len(x) for x in ln[:count]], dtype=np.uint64)
-    assert _fits(ioff, ln[:count], inp.numel()) and _fits(ooff, worst, out.numel())
+    _flat(inp, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff), (pioff, pln, pooff), count = _ragged(
+        inp, in_off, n, out, out_off, room=lambda ln: np.array([snap_max_len(x) for x in ln], dtype=np.uint64))
+    _words(count, out_len, size=8)
     check(_lib.lib().chips_snap_ragged_dev(_p(inp), pioff, pln, count, _p(out), pooff, _p(out_len), _p(scratch),
                                            scratch.numel(), _stream()))
 
@@ -1188,16 +1035,12 @@ def unsnap_ragged(inp: torch.Tensor, in_off, in_len, out: torch.Tensor, out_off,
     decompressed byte: untouched for a framing error or a small capacity, zeros
     for a block that does not decode or whose CRC disagrees.  Enqueued on the
     current stream, not synchronised."""
-    assert inp.is_cuda and out.is_cuda and out_len.is_cuda and status.is_cuda and scratch.is_cuda
-    assert inp.dtype == out.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ln, pln, nl = _arr(in_len)
-    ooff, pooff, no = _arr(out_off)
-    cap, pcap, nc = _arr(out_cap)
-    assert nl == count == no == nc
-    assert out_len.numel() >= count and out_len.element_size() == 8 and out_len.is_contiguous()
-    assert status.numel() >= count and status.element_size() == 4 and status.is_contiguous()
-    assert _fits(ioff, ln[:count], inp.numel()) and _fits(ooff, cap[:count], out.numel())
+    _flat(inp, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff, cap), (pioff, pln, pooff, pcap), count = _ragged(inp, in_off, in_len, out, out_off, out_cap,
+                                                                      kinds="Q", room=lambda ln, cap: cap)
+    _words(count, out_len, size=8)
+    _words(count, status)
     check(_lib.lib().chips_unsnap_ragged_dev(_p(inp), pioff, pln, count, _p(out), pooff, pcap, _p(out_len), _p(status),
                                              _p(scratch), scratch.numel(), _stream()))
 
@@ -1207,11 +1050,9 @@ def snap_encode_layout(fmt: int, sizes, align: int = 256, stream_offset: int = S
     ragged_layout over the worst-case lengths, since the encoded length depends
     on the data.  Returns (out_off, out_cap, total)."""
     n, pn, count = _arr(sizes)
-    off, cap = np.zeros(max(count, 1), dtype=np.uint64), np.zeros(max(count, 1), dtype=np.uint64)
-    total = ctypes.c_uint64()
-    check(_lib.lib().chips_encode_layout(fmt, pn, count, align, stream_offset, off.ctypes.data_as(_lib.c_u64p),
-                                         cap.ctypes.data_as(_lib.c_u64p), ctypes.byref(total)))
-    return off[:count].tolist(), cap[:count].tolist(), total.value
+    (off, poff), (cap, pcap), total = _out(count), _out(count), ctypes.c_uint64()
+    check(_lib.lib().chips_encode_layout(fmt, pn, count, align, stream_offset, poff, pcap, ctypes.byref(total)))
+    return off.tolist(), cap.tolist(), total.value
 
 
 def snap_ragged_scratch(fmt: int, lens, out_cap=None, device=None) -> torch.Tensor:
@@ -1223,7 +1064,7 @@ def snap_ragged_scratch(fmt: int, lens, out_cap=None, device=None) -> torch.Tens
     else:
         cap, pcap, _ = _arr(out_cap)
         size = _lib.lib().chips_decode_scratch_len(fmt, pln, pcap, count)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(size, device)
 
 
 def encode_ragged_snap(fmt: int, inp: torch.Tensor, in_off, sizes, out: torch.Tensor, out_off, hashes: torch.Tensor,
@@ -1235,23 +1076,17 @@ def encode_ragged_snap(fmt: int, inp: torch.Tensor, in_off, sizes, out: torch.Te
     snap_encode_layout(fmt, sizes).  Stream bytes, hash and EncodeInfo are
     those of encode() at fmt.  Returns (encoded length per object, EncodeInfo
     per object)."""
-    from .structs import EncodeInfo
-    assert inp.is_cuda and out.is_cuda and hashes.is_cuda and scratch.is_cuda
-    assert inp.dtype == out.dtype == torch.uint8 and inp.is_contiguous() and out.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ln, pln, nl = _arr(sizes)
-    ooff, pooff, no = _arr(out_off)
-    assert nl == count == no and hashes.numel() >= 32 * count and hashes.is_contiguous()
-    assert _fits(ioff, ln[:count], inp.numel())
+    _flat(inp, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff), (pioff, pln, pooff), count = _ragged(inp, in_off, sizes, out, out_off, room=None)
+    _hashes(hashes, count)
     assert scratch.numel() >= _lib.lib().chips_encode_scratch_len(fmt, pln, count)
     inj, keep = _inject_array(inject, count)
-    olen = (ctypes.c_uint64 * max(count, 1))()
-    info = (_lib.EncodeInfoC * max(count, 1))()
+    olen, polen, info = _encode_outputs(count)
     pk = bytes(pubkey) if pubkey is not None else None
     check(_lib.lib().chips_encode_ragged_dev(fmt, pk, len(pk) if pk else 0, inj, _p(inp), pioff, pln, count, _p(out),
-                                             pooff, olen, _p(hashes), info, _p(scratch), _stream()))
-    assert all(int(a) + b <= out.numel() for a, b in zip(ooff[:count], list(olen)[:count]))
-    return list(olen)[:count], [EncodeInfo.from_c(info[o]) for o in range(count)]
+                                             pooff, polen, _p(hashes), info, _p(scratch), _stream()))
+    return _encoded(olen, info, ooff, out)
 
 
 def decode_ragged_snap(fmt: int, enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, out: torch.Tensor,
@@ -1263,17 +1098,12 @@ def decode_ragged_snap(fmt: int, enc: torch.Tensor, in_off, in_len, hashes: torc
     the bao / ecies status of an object that failed there (not decompressed,
     nothing written), or a snappy status; out_len[o] (int64 on the device): the
     decoded length.  Without the Ecies bit nothing is waited for."""
-    assert enc.is_cuda and out.is_cuda and status.is_cuda and scratch.is_cuda and out_len.is_cuda
-    assert enc.dtype == out.dtype == torch.uint8 and enc.is_contiguous() and out.is_contiguous()
-    ioff, pioff, count = _arr(in_off)
-    ln, pln, nl = _arr(in_len)
-    ooff, pooff, no = _arr(out_off)
-    cap, pcap, nc = _arr(out_cap)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    assert nl == count == no == npad == nc and _fits(ioff, ln[:count], enc.numel())
-    assert _fits(ooff, cap[:count], out.numel())
-    assert status.numel() >= count and status.element_size() == 4 and status.is_contiguous()
-    assert out_len.numel() >= count and out_len.element_size() == 8 and out_len.is_contiguous()
+    _flat(enc, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff, cap, pad), (pioff, pln, pooff, pcap, ppad), count = _ragged(
+        enc, in_off, in_len, out, out_off, out_cap, padding, kinds="QI", room=lambda ln, cap, pad: cap)
+    _words(count, status)
+    _words(count, out_len, size=8)
     assert scratch.numel() >= _lib.lib().chips_decode_scratch_len(fmt, pln, pcap, count)
     sk = bytes(secret_key) if secret_key is not None else None
     check(_lib.lib().chips_decode_ragged_dev(fmt, sk, len(sk) if sk else 0, _p(enc), pioff, pln, count,
@@ -1285,35 +1115,29 @@ def decode_ragged_snap(fmt: int, enc: torch.Tensor, in_off, in_len, hashes: torc
 # (include/carbonado_hip_fread.h): the frame index of resident streams, its
 # proof against the stream, the read
 
-def _stream_args(streams, in_off, in_len, hashes, padding, chunk_len):
-    assert streams.is_cuda and hashes.is_cuda and streams.dtype == torch.uint8
-    assert streams.is_contiguous() and hashes.is_contiguous()
-    ioff, pioff, nstreams = _arr(in_off)
-    ilen, pilen, nl = _arr(in_len)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    cl, pcl, ncl = _arr(chunk_len, np.uint32)
-    assert nl == nstreams == npad == ncl
-    assert hashes.numel() >= 32 * nstreams and _fits(ioff, ilen[:nstreams], streams.numel())
-    return (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams
-
-
 def _frame_keys(fmt, keys, ivs, key_status, nstreams):
     """(keep-alive, keys pointer, ivs pointer, key_status pointer): looked at for format 15 only"""
     if fmt != 15 or keys is None:
         return None, None, None, None
-    kk, pk, vv, pv = _gcm_keys(keys, ivs, nstreams)
-    ks, pks = None, None
-    if key_status is not None:
-        ks, pks, nks = _arr(key_status, np.uint32)
-        assert nks == nstreams
-    return (kk, vv, ks), pk, pv, pks
+    kv, (pk, pv), _ = _gcm_keys(keys, ivs, nstreams)
+    ks, pks = _opt(key_status, nstreams)
+    return (kv, ks), pk, pv, pks
+
+
+def _index_args(frame_off, idx_off, nframes, *more, kinds=""):
+    """The index of every stream, frame_off[idx_off[s] : idx_off[s] + nframes[s]
+    + 1], with further per-stream columns: (fo, (io, nf, ...)), their pointers
+    alike, nstreams."""
+    fo, pfo, nfo = _arr(frame_off)
+    cols, ptrs, nstreams = _cols("QQ" + kinds, idx_off, nframes, *more)
+    assert not nstreams or (nfo and _fits(cols[0], cols[1], nfo - 1))  # idx_off + nframes + 1 <= len(frame_off)
+    return (fo, cols), (pfo, ptrs), nstreams
 
 
 def frame_index_scratch(nstreams: int, nentries: int, device=None) -> torch.Tensor:
     """Scratch of a frame_index or verify_frame_index call over nstreams streams
     and nentries index entries in all (the capacities, or nframes + 1 each)."""
-    size = _lib.lib().chipf_index_scratch_len(nstreams, nentries)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(_lib.lib().chipf_index_scratch_len(nstreams, nentries), device)
 
 
 def frame_index(fmt: int, streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len, idx_off,
@@ -1329,23 +1153,18 @@ def frame_index(fmt: int, streams: torch.Tensor, in_off, in_len, hashes: torch.T
     7 with a vouch bit for a stream whose header's primary copy is damaged
     (scrub_ragged, then call again)."""
     (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
-                                                                              chunk_len)
-    io, pio, nio = _arr(idx_off)
-    cap, pcap, ncap = _arr(idx_cap)
-    assert nio == nstreams == ncap and scratch.is_cuda
-    total = int((io[:nstreams] + cap[:nstreams]).max()) if nstreams else 0
-    frame_off = np.zeros(max(total, 1), dtype=np.uint64)
-    nframes = np.zeros(max(nstreams, 1), dtype=np.uint64)
-    status = np.zeros(max(nstreams, 1), dtype=np.uint32)
-    plain = np.zeros(max(nstreams, 1), dtype=np.uint64)
-    vouch = np.zeros(max(nstreams, 1), dtype=np.uint32)
+                                                                              chunk_len, one_dim=False)
+    _resident(scratch)
+    (io, cap), (pio, pcap), nidx = _cols("QQ", idx_off, idx_cap)
+    assert nidx == nstreams
+    (frame_off, pfo), (nframes, pnf) = _out(int((io + cap).max()) if nstreams else 0), _out(nstreams)
+    (status, pstatus), (vouch, pvouch) = _out(nstreams, np.uint32), _out(nstreams, np.uint32)
+    plain, pplain = _out(nstreams)
     keep, pk, pv, pks = _frame_keys(fmt, keys, ivs, key_status, nstreams)
     check(_lib.lib().chipf_frame_index_dev(fmt, pk, pv, pks, _p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams,
-                                           frame_off.ctypes.data_as(_lib.c_u64p), pio, pcap,
-                                           nframes.ctypes.data_as(_lib.c_u64p), status.ctypes.data_as(_lib.c_u32p),
-                                           plain.ctypes.data_as(_lib.c_u64p), vouch.ctypes.data_as(_lib.c_u32p),
-                                           _p(scratch), scratch.numel(), _stream()))
-    return frame_off[:total], nframes[:nstreams], status[:nstreams], plain[:nstreams], vouch[:nstreams]
+                                           pfo, pio, pcap, pnf, pstatus, pplain, pvouch, _p(scratch), scratch.numel(),
+                                           _stream()))
+    return frame_off, nframes, status, plain, vouch
 
 
 def verify_frame_index(fmt: int, streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len,
@@ -1360,14 +1179,12 @@ def verify_frame_index(fmt: int, streams: torch.Tensor, in_off, in_len, hashes: 
     link; 11 for a chain that is not canonical.  Enqueued on the current stream,
     not synchronised."""
     (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
-                                                                              chunk_len)
-    fo, pfo, nfo = _arr(frame_off)
-    io, pio, nio = _arr(idx_off)
-    nf, pnf, nnf = _arr(nframes)
-    assert nio == nstreams == nnf and scratch.is_cuda
-    assert all(int(io[s]) + int(nf[s]) + 1 <= nfo for s in range(nstreams))
-    for t, size in ((index_status, 4), (plain_len, 8), (index_vouch, 4)):
-        assert t.is_cuda and t.numel() >= nstreams and t.element_size() == size and t.is_contiguous()
+                                                                              chunk_len, one_dim=False)
+    _resident(scratch)
+    (fo, (io, nf)), (pfo, (pio, pnf)), nidx = _index_args(frame_off, idx_off, nframes)
+    assert nidx == nstreams
+    _words(nstreams, index_status, index_vouch)
+    _words(nstreams, plain_len, size=8)
     keep, pk, pv, pks = _frame_keys(fmt, keys, ivs, key_status, nstreams)
     check(_lib.lib().chipf_verify_index_dev(fmt, pk, pv, pks, _p(streams), pioff, pilen, _p(hashes), ppad, pcl, nstreams,
                                             pfo, pio, pnf, _p(index_status), _p(plain_len), _p(index_vouch),
@@ -1380,33 +1197,21 @@ def frame_read_layout(fmt: int, chunk_len, padding, frame_off, idx_off, nframes,
     length)) of every request and what its scratch depends on (host only):
     (content_off, content_len, content_total, nseg, stage_total, vseg).
     index_status: as read_frame_ranges takes it."""
-    cl, pcl, nstreams = _arr(chunk_len, np.uint32)
-    pad, ppad, npad = _arr(padding, np.uint32)
-    fo, pfo, nfo = _arr(frame_off)
-    io, pio, nio = _arr(idx_off)
-    nf, pnf, nnf = _arr(nframes)
-    pl, ppl, npl = _arr(plain_len)
-    rs, prs, nreq = _arr(req_stream, np.uint32)
-    st, pst, ns = _arr(start)
-    ln, pln, nl = _arr(length)
-    assert npad == nstreams == nio == nnf == npl and ns == nreq == nl
-    assert all(int(io[s]) + int(nf[s]) + 1 <= nfo for s in range(nstreams))
-    off, clen = np.zeros(max(nreq, 1), dtype=np.uint64), np.zeros(max(nreq, 1), dtype=np.uint64)
+    (fo, (io, nf, pl, cl, pad)), (pfo, (pio, pnf, ppl, pcl, ppad)), nstreams = _index_args(
+        frame_off, idx_off, nframes, plain_len, chunk_len, padding, kinds="QII")
+    (rs, st, ln), (prs, pst, pln), nreq = _cols("IQQ", req_stream, start, length)
+    ist, pis = _opt(index_status, nstreams)
+    (off, poff), (clen, pclen) = _out(nreq), _out(nreq)
     total, nseg, stage, vseg = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    pis = None
-    if index_status is not None:
-        ist, pis, nis = _arr(index_status, np.uint32)
-        assert nis == nstreams
     check(_lib.lib().chipf_read_layout(fmt, pcl, ppad, pis, pfo, pio, pnf, ppl, nstreams, prs, pst, pln, nreq, align,
-                                       off.ctypes.data_as(_lib.c_u64p), clen.ctypes.data_as(_lib.c_u64p),
-                                       ctypes.byref(total), ctypes.byref(nseg), ctypes.byref(stage), ctypes.byref(vseg)))
-    return off[:nreq].tolist(), clen[:nreq].tolist(), total.value, nseg.value, stage.value, vseg.value
+                                       poff, pclen, ctypes.byref(total), ctypes.byref(nseg), ctypes.byref(stage),
+                                       ctypes.byref(vseg)))
+    return off.tolist(), clen.tolist(), total.value, nseg.value, stage.value, vseg.value
 
 
 def frame_read_scratch(nreq: int, nseg: int, stage_total: int, vseg: int, nstreams: int, device=None) -> torch.Tensor:
     """Scratch of a read_frame_ranges call (the numbers of frame_read_layout)."""
-    size = _lib.lib().chipf_read_scratch_len(nreq, nseg, stage_total, vseg, nstreams)
-    return torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    return _scratch(_lib.lib().chipf_read_scratch_len(nreq, nseg, stage_total, vseg, nstreams), device)
 
 
 def read_frame_ranges(fmt: int, streams: torch.Tensor, in_off, in_len, hashes: torch.Tensor, padding, chunk_len,
@@ -1425,36 +1230,20 @@ def read_frame_ranges(fmt: int, streams: torch.Tensor, in_off, in_len, hashes: t
     them.  The GCM tag is NOT checked.  Enqueued on the current stream, not
     synchronised.  Returns the content length per request."""
     (ioff, ilen, pad, cl), (pioff, pilen, ppad, pcl), nstreams = _stream_args(streams, in_off, in_len, hashes, padding,
-                                                                              chunk_len)
-    assert content.is_cuda and status.is_cuda and used.is_cuda and vouch.is_cuda and scratch.is_cuda
-    assert content.dtype == torch.uint8 and content.dim() == 1 and content.is_contiguous()
-    fo, pfo, nfo = _arr(frame_off)
-    io, pio, nio = _arr(idx_off)
-    nf, pnf, nnf = _arr(nframes)
-    pl, ppl, npl = _arr(plain_len)
-    rs, prs, nreq = _arr(req_stream, np.uint32)
-    st, pst, ns = _arr(start)
-    ln, pln, nln = _arr(length)
-    coff, pcoff, nco = _arr(content_off)
-    assert nio == nstreams == nnf == npl and ns == nreq == nln == nco
-    assert all(int(io[s]) + int(nf[s]) + 1 <= nfo for s in range(nstreams))
-    for t in (status, used, vouch):
-        assert t.numel() >= nreq and t.element_size() == 4 and t.is_contiguous()
-    if nreq and int(rs.max()) < nstreams:  # the content buffer is checked before the call (else: the call reports it)
-        want = np.array([min(max(int(pl[s]) - int(a), 0), int(n)) for s, a, n in zip(rs[:nreq], st[:nreq], ln[:nreq])],
-                        dtype=np.uint64)
-        assert _fits(coff, want, content.numel())
+                                                                              chunk_len, one_dim=False)
+    _resident(scratch)
+    (fo, (io, nf, pl)), (pfo, (pio, pnf, ppl)), nidx = _index_args(frame_off, idx_off, nframes, plain_len, kinds="Q")
+    assert nidx == nstreams
+    (rs, st, ln, coff, clen), (prs, pst, pln, pcoff, pclen), nreq = _request_args(
+        req_stream, start, length, content_off, content, (status, used, vouch), nstreams,
+        lambda rs, st, ln: np.minimum(np.where(pl[rs] > st, pl[rs] - st, np.uint64(0)), ln))
     keep, pk, pv, _ = _frame_keys(fmt, keys, ivs, None, nstreams)
-    pis = None
-    if index_status is not None:
-        ist, pis, nis = _arr(index_status, np.uint32)
-        assert nis == nstreams
-    clen = np.zeros(max(nreq, 1), dtype=np.uint64)
+    ist, pis = _opt(index_status, nstreams)
     check(_lib.lib().chipf_read_ranges_dev(fmt, pk, pv, pis, pfo, pio, pnf, ppl, _p(streams), pioff, pilen, _p(hashes),
-                                           ppad, pcl, nstreams, prs, pst, pln, nreq, _p(content), pcoff,
-                                           clen.ctypes.data_as(_lib.c_u64p), _p(status), _p(used), _p(vouch), flags,
-                                           _p(scratch), scratch.numel(), _stream()))
-    return clen[:nreq].tolist()
+                                           ppad, pcl, nstreams, prs, pst, pln, nreq, _p(content), pcoff, pclen,
+                                           _p(status), _p(used), _p(vouch), flags, _p(scratch), scratch.numel(),
+                                           _stream()))
+    return clen.tolist()
 
 
 def host_topology() -> dict:

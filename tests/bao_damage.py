@@ -5,6 +5,7 @@ top-down recursion (oracle/pyoracle.py) or with the library's tree
 arithmetic, and the closed form of which zfec shards a damaged node spoils."""
 from __future__ import annotations
 
+import functools
 from typing import NamedTuple
 
 
@@ -41,6 +42,29 @@ def tree_nodes(n: int) -> list[Node]:
         out.append(Node(off, size, lo, hi, lv))
         off += size
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_offsets(spc: int) -> tuple[int, ...]:
+    """Stream offset of every chunk of a Zfec|Bao stream of eight shards of spc
+    chunks each, from tree_nodes."""
+    return tuple(nd.off for nd in tree_nodes(8192 * spc) if not nd.parent)
+
+
+def chunk_off(i: int, N: int) -> int:
+    """Stream offset of chunk i of a bao stream of N full chunks (pre-order):
+    a walk down from the root, a second derivation that is kept apart from
+    chunk_offsets on purpose."""
+    off, lo, cnt = 8, 0, N
+    while cnt > 1:
+        off += 64
+        left = 1 << ((cnt - 1).bit_length() - 1)
+        if i < lo + left:
+            cnt = left
+        else:
+            off += left * 1024 + 64 * (left - 1)
+            lo, cnt = lo + left, cnt - left
+    return off
 
 
 def shards_missing(node: Node, spc: int) -> set[int]:

@@ -4,15 +4,14 @@ through ctypes on the libcrypto the library already links; the reads with
 slices of the test's own plaintexts, encoded by encode_ragged_ecies with
 injected ephemeral secrets and nonces.  Every comparison is of whole buffers
 over a canary fill, so the bytes outside the ranges are checked too."""
-import ctypes
-import ctypes.util
 import functools
 
 import numpy as np
 import pytest
 import torch
 
-import bao_damage as B  # tests/bao_damage.py (tests/ is on sys.path under pytest)
+from evp_gcm import evp_seal, j0_of  # tests/evp_gcm.py (tests/ is on sys.path under pytest)
+from read_world import PlainStreams, dev, up16
 
 pytestmark = pytest.mark.gpu
 
@@ -22,69 +21,6 @@ EDGES = [0, 1, 15, 16, 17, 31, 32, 33]
 SECRET = bytes(range(1, 33))
 WRAP_KEY = bytes.fromhex("c675bea6d150367b0fa6dbcb7e142508528234103f6d178e38a1ab8736270c09")
 WRAP_IV = bytes.fromhex("5436aa0234896411575d56bbd2095dc7")
-
-_C = ctypes.CDLL(ctypes.util.find_library("crypto") or "libcrypto.so.3")
-_C.EVP_CIPHER_CTX_new.restype = ctypes.c_void_p
-_C.EVP_aes_256_gcm.restype = ctypes.c_void_p
-_C.EVP_aes_256_ecb.restype = ctypes.c_void_p
-_GCM_SET_IVLEN, _GCM_GET_TAG = 0x9, 0x10
-
-
-def evp_seal(key: bytes, iv: bytes, pt: bytes):
-    """(ciphertext, tag) of EVP AES-256-GCM with a 16-byte IV and no AAD."""
-    ctx = ctypes.c_void_p(_C.EVP_CIPHER_CTX_new())
-    out = ctypes.create_string_buffer(len(pt) + 16)
-    n, tag = ctypes.c_int(0), ctypes.create_string_buffer(16)
-    try:
-        assert _C.EVP_EncryptInit_ex(ctx, ctypes.c_void_p(_C.EVP_aes_256_gcm()), None, None, None) == 1
-        assert _C.EVP_CIPHER_CTX_ctrl(ctx, _GCM_SET_IVLEN, 16, None) == 1
-        assert _C.EVP_EncryptInit_ex(ctx, None, None, key, iv) == 1
-        total = 0
-        if pt:
-            assert _C.EVP_EncryptUpdate(ctx, out, ctypes.byref(n), pt, len(pt)) == 1
-            total = n.value
-        fin = ctypes.create_string_buffer(16)
-        assert _C.EVP_EncryptFinal_ex(ctx, fin, ctypes.byref(n)) == 1 and n.value == 0
-        assert _C.EVP_CIPHER_CTX_ctrl(ctx, _GCM_GET_TAG, 16, tag) == 1
-    finally:
-        _C.EVP_CIPHER_CTX_free(ctx)
-    assert total == len(pt)
-    return out.raw[:total], tag.raw
-
-
-def evp_ecb(key: bytes, block: bytes) -> bytes:
-    ctx = ctypes.c_void_p(_C.EVP_CIPHER_CTX_new())
-    out, n = ctypes.create_string_buffer(32), ctypes.c_int(0)
-    try:
-        assert _C.EVP_EncryptInit_ex(ctx, ctypes.c_void_p(_C.EVP_aes_256_ecb()), None, key, None) == 1
-        _C.EVP_CIPHER_CTX_set_padding(ctx, 0)
-        assert _C.EVP_EncryptUpdate(ctx, out, ctypes.byref(n), block, 16) == 1
-    finally:
-        _C.EVP_CIPHER_CTX_free(ctx)
-    return out.raw[:16]
-
-
-def gf128_mul(x: int, y: int) -> int:
-    """SP 800-38D algorithm 1 on Python integers (bit 127 = the block's first bit)."""
-    z, v = 0, y
-    for i in range(128):
-        if (x >> (127 - i)) & 1:
-            z ^= v
-        v = (v >> 1) ^ (0xE1 << 120) if v & 1 else v >> 1
-    return z
-
-
-def j0_of(key: bytes, iv: bytes) -> int:
-    h = int.from_bytes(evp_ecb(key, bytes(16)), "big")
-    return gf128_mul(gf128_mul(int.from_bytes(iv, "big"), h) ^ 128, h)
-
-
-def up16(x: int) -> int:
-    return (x + 15) // 16 * 16
-
-
-def dev(a) -> torch.Tensor:
-    return torch.from_numpy(np.array(a, dtype=np.uint8)).cuda()
 
 
 # ---- the keystream over ranges ------------------------------------------------------
@@ -175,12 +111,7 @@ SIZES = [0, 1, 926, 927, 928, 5000, 70001, 300001]
 BIG = 6  # the stream the damage cases use
 
 
-@functools.lru_cache(maxsize=None)
-def _chunk_offsets(spc: int):
-    return tuple(nd.off for nd in B.tree_nodes(8192 * spc) if not nd.parent)
-
-
-class Streams:
+class Streams(PlainStreams):
     def __init__(self):
         from carbonado_amd import device as D
         from oracle import oracle as O
@@ -191,16 +122,9 @@ class Streams:
         self.inject = [(rng.integers(1, 256, 32, dtype=np.uint8).tobytes(), rng.integers(0, 256, 16, dtype=np.uint8).tobytes())
                        for _ in SIZES]
         self.env = [O.c_ecies_encrypt(self.pub, p, sk, nonce) for p, (sk, nonce) in zip(self.pt, self.inject)]
-        in_off, at = [], 0
-        for n in SIZES:
-            in_off.append(at)
-            at += up16(n) + 16
-        plain = np.full(at + 16, 0x11, dtype=np.uint8)
-        for o, n in enumerate(SIZES):
-            plain[in_off[o]:in_off[o] + n] = np.frombuffer(self.pt[o], dtype=np.uint8)
+        in_off, plain = self.place_plain(SIZES)
         self.off, _, total = D.ragged_layout(12, [n + 97 for n in SIZES], 256)
-        self.out = torch.full((total + 64,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.hashes = torch.full((self.count, 32), 0xEE, dtype=torch.uint8, device="cuda")
+        self.make_outputs(total, self.count)
         self.olen, info = D.encode_ragged_ecies(13, self.pub, dev(plain), in_off, SIZES, self.out, self.off, self.hashes,
                                                 D.ecies_ragged_scratch(13, SIZES), inject=self.inject)
         torch.cuda.synchronize()
@@ -218,11 +142,8 @@ class Streams:
 
     def damaged(self, s, chunks, byte=500):
         """A copy of the streams with one byte flipped in each of stream s's chunks given as (shard, chunk)."""
-        out = self.out.clone()
         spc = self.cls[s] // 1024
-        for shard, c in chunks:
-            out[self.off[s] + _chunk_offsets(spc)[shard * spc + c] + byte] ^= 0x40
-        return out
+        return self.flipped(self.chunk_pos(s, shard * spc + c, byte) for shard, c in chunks)
 
     def stream_keys(self, out=None, secret=SECRET):
         from carbonado_amd import device as D
@@ -242,13 +163,6 @@ class Streams:
         torch.cuda.synchronize()
         assert got == clen
         return content.cpu().numpy(), st.cpu().tolist(), used.cpu().tolist(), vouch.cpu().tolist(), coff, clen
-
-    def want(self, reqs, coff, size, zero=()):
-        img = np.full(size, 0xA5, dtype=np.uint8)
-        for r, (s, a, n) in enumerate(reqs):
-            part = np.frombuffer(self.pt[s][a:a + n], dtype=np.uint8)
-            img[coff[r]:coff[r] + part.size] = 0 if r in zero else part
-        return img
 
 
 @functools.lru_cache(maxsize=None)

@@ -4,13 +4,14 @@ libcrypto the library already links: a reference that shares nothing with the
 bitsliced AES and the table-free GHASH under test.  Every comparison is of
 whole buffers, so the bytes between the output ranges (a canary fill) are
 checked with the ranges themselves."""
-import ctypes
-import ctypes.util
 import math
 
 import numpy as np
 import pytest
 import torch
+
+from evp_gcm import evp_seal, j0_of  # tests/evp_gcm.py (tests/ is on sys.path under pytest)
+from read_world import dev, up16
 
 pytestmark = pytest.mark.gpu
 
@@ -19,65 +20,6 @@ ITEM = 8192                   # bytes of one wave's item (gcm_device.hpp: SPAN *
 LEVEL2 = 64 * ITEM            # 64 items: one step of the second level
 EDGES = [0, 1, 15, 16, 17, 31, 32, 33, 1023, 1024, 1025, 2047, 2048, 2049, ITEM - 1, ITEM, ITEM + 1,
          2 * ITEM - 1, 2 * ITEM, 2 * ITEM + 1, LEVEL2 - 1, LEVEL2, LEVEL2 + 1]
-
-_C = ctypes.CDLL(ctypes.util.find_library("crypto") or "libcrypto.so.3")
-_C.EVP_CIPHER_CTX_new.restype = ctypes.c_void_p
-_C.EVP_aes_256_gcm.restype = ctypes.c_void_p
-_C.EVP_aes_256_ecb.restype = ctypes.c_void_p
-_GCM_SET_IVLEN, _GCM_GET_TAG = 0x9, 0x10
-
-
-def evp_seal(key: bytes, iv: bytes, pt: bytes):
-    """(ciphertext, tag) of EVP AES-256-GCM with a 16-byte IV and no AAD."""
-    ctx = ctypes.c_void_p(_C.EVP_CIPHER_CTX_new())
-    out = ctypes.create_string_buffer(len(pt) + 16)
-    n, tag = ctypes.c_int(0), ctypes.create_string_buffer(16)
-    try:
-        assert _C.EVP_EncryptInit_ex(ctx, ctypes.c_void_p(_C.EVP_aes_256_gcm()), None, None, None) == 1
-        assert _C.EVP_CIPHER_CTX_ctrl(ctx, _GCM_SET_IVLEN, 16, None) == 1
-        assert _C.EVP_EncryptInit_ex(ctx, None, None, key, iv) == 1
-        total = 0
-        if pt:
-            assert _C.EVP_EncryptUpdate(ctx, out, ctypes.byref(n), pt, len(pt)) == 1
-            total = n.value
-        fin = ctypes.create_string_buffer(16)
-        assert _C.EVP_EncryptFinal_ex(ctx, fin, ctypes.byref(n)) == 1 and n.value == 0
-        assert _C.EVP_CIPHER_CTX_ctrl(ctx, _GCM_GET_TAG, 16, tag) == 1
-    finally:
-        _C.EVP_CIPHER_CTX_free(ctx)
-    assert total == len(pt)
-    return out.raw[:total], tag.raw
-
-
-def evp_ecb(key: bytes, block: bytes) -> bytes:
-    ctx = ctypes.c_void_p(_C.EVP_CIPHER_CTX_new())
-    out, n = ctypes.create_string_buffer(32), ctypes.c_int(0)
-    try:
-        assert _C.EVP_EncryptInit_ex(ctx, ctypes.c_void_p(_C.EVP_aes_256_ecb()), None, key, None) == 1
-        _C.EVP_CIPHER_CTX_set_padding(ctx, 0)
-        assert _C.EVP_EncryptUpdate(ctx, out, ctypes.byref(n), block, 16) == 1
-    finally:
-        _C.EVP_CIPHER_CTX_free(ctx)
-    return out.raw[:16]
-
-
-def gf128_mul(x: int, y: int) -> int:
-    """SP 800-38D algorithm 1 on Python integers (bit 127 = the block's first bit)."""
-    z, v = 0, y
-    for i in range(128):
-        if (x >> (127 - i)) & 1:
-            z ^= v
-        v = (v >> 1) ^ (0xE1 << 120) if v & 1 else v >> 1
-    return z
-
-
-def j0_of(key: bytes, iv: bytes) -> int:
-    h = int.from_bytes(evp_ecb(key, bytes(16)), "big")
-    return gf128_mul(gf128_mul(int.from_bytes(iv, "big"), h) ^ 128, h)
-
-
-def up16(x: int) -> int:
-    return (x + 15) // 16 * 16
 
 
 class Batch:
@@ -118,10 +60,6 @@ class Batch:
         for o, n in enumerate(self.lens):
             img[self.out_off[o]:self.out_off[o] + n] = np.frombuffer(self.ct[o], dtype=np.uint8)
         return img
-
-
-def dev(a: np.ndarray) -> torch.Tensor:
-    return torch.from_numpy(np.array(a, dtype=np.uint8)).cuda()
 
 
 def seal(b: Batch, fill=0xA5):

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-import bao_damage as B  # tests/bao_damage.py (tests/ is on sys.path under pytest)
-import snap_data as SD
+import snap_data as SD  # tests/snap_data.py (tests/ is on sys.path under pytest)
+from read_world import PlainStreams, dev, up16
 
 pytestmark = pytest.mark.gpu
 
@@ -65,20 +65,7 @@ def walk(frame: bytes):
     return off + [pos], plain
 
 
-def up16(x: int) -> int:
-    return (x + 15) // 16 * 16
-
-
-def dev(a) -> torch.Tensor:
-    return torch.from_numpy(np.array(a, dtype=np.uint8)).cuda()
-
-
-@functools.lru_cache(maxsize=None)
-def _chunk_offsets(spc: int):
-    return tuple(nd.off for nd in B.tree_nodes(8192 * spc) if not nd.parent)
-
-
-class Streams:
+class Streams(PlainStreams):
     def __init__(self, fmt):
         from carbonado_amd import device as D
         from carbonado_amd import encoding as E
@@ -95,16 +82,9 @@ class Streams:
         self.pub = E.public_key(SECRET)
         self.inject = [(rng.integers(1, 256, 32, dtype=np.uint8).tobytes(),
                         rng.integers(0, 256, 16, dtype=np.uint8).tobytes()) for _ in SIZES]
-        in_off, at = [], 0
-        for n in SIZES:
-            in_off.append(at)
-            at += up16(n) + 16
-        plain = np.full(at + 16, 0x11, dtype=np.uint8)
-        for o, n in enumerate(SIZES):
-            plain[in_off[o]:in_off[o] + n] = np.frombuffer(self.pt[o], dtype=np.uint8)
+        in_off, plain = self.place_plain(SIZES)
         self.off, self.cap, total = D.snap_encode_layout(fmt, SIZES, 256)
-        self.out = torch.full((total + 64,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.hashes = torch.full((self.count, 32), 0xEE, dtype=torch.uint8, device="cuda")
+        self.make_outputs(total, self.count)
         self.olen, info = D.encode_ragged_snap(fmt, dev(plain), in_off, SIZES, self.out, self.off, self.hashes,
                                                D.snap_ragged_scratch(fmt, SIZES), pubkey=self.pub if fmt == 15 else None,
                                                inject=self.inject if fmt == 15 else None)
@@ -129,13 +109,10 @@ class Streams:
     # ---- damage
     def stream_pos(self, s, x):
         """Where byte x of stream s's content (object byte x, or shard i's column c at i C + c) lies in the stream."""
-        return self.off[s] + _chunk_offsets(self.cls[s] // 1024)[x // 1024] + x % 1024
+        return self.chunk_pos(s, x // 1024, x % 1024)
 
     def damaged(self, s, content_bytes):
-        out = self.out.clone()
-        for x in content_bytes:
-            out[self.stream_pos(s, x)] ^= 0x40
-        return out
+        return self.flipped(self.stream_pos(s, x) for x in content_bytes)
 
     # ---- the calls
     def build(self, caps=None, out=None, keys=None):
@@ -183,13 +160,6 @@ class Streams:
         torch.cuda.synchronize()
         assert got == clen
         return content.cpu().numpy(), st.cpu().tolist(), used.cpu().tolist(), vouch.cpu().tolist(), coff, clen
-
-    def want(self, reqs, coff, size, zero=(), pt=None):
-        img = np.full(size, 0xA5, dtype=np.uint8)
-        for r, (s, a, n) in enumerate(reqs):
-            part = np.frombuffer((pt or self.pt)[s][a:a + n], dtype=np.uint8)
-            img[coff[r]:coff[r] + part.size] = 0 if r in zero else part
-        return img
 
 
 @functools.lru_cache(maxsize=None)

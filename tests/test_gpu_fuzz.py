@@ -8,6 +8,7 @@ test fails; the seeds are fixed, so a failure reproduces."""
 import numpy as np
 import pytest
 
+from bao_damage import chunk_off  # tests/bao_damage.py (tests/ is on sys.path under pytest)
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -144,20 +145,6 @@ def test_every_level_compressible_random(gpu, case):
     assert enc == oenc and h == oh, (level, n)
     assert info.padding_len == oinfo["padding_len"], (level, n)
     assert ca.decode(sk, h, enc, info.padding_len, level) == d, (level, n)
-
-
-def chunk_off(i: int, N: int) -> int:
-    """Stream offset of chunk i of an N-chunk bao stream: 8 + 1024 i + 64 (P(i) + c(i))."""
-    def clog2(x):
-        return 0 if x <= 1 else (x - 1).bit_length()
-    cl = clog2(N - i)
-    c = cl if i == 0 else min((i & -i).bit_length() - 1, cl)
-    total, cnt, L = 0, N, 1
-    while cnt > 1:
-        total += min((i + (1 << L) - 1) >> L, cnt // 2)
-        cnt = (cnt + 1) // 2
-        L += 1
-    return 8 + 1024 * i + 64 * (total + c)
 
 
 @pytest.mark.parametrize("case", range(12))

@@ -23,7 +23,9 @@ import functools
 import numpy as np
 import pytest
 
-from test_gpu_qread import CANARY, GUARD, Got, _check_canary, assert_equal, chunk_off
+import read_world as RW  # tests/read_world.py (tests/ is on sys.path under pytest)
+from bao_damage import chunk_off
+from read_world import CANARY, Got, assert_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -118,53 +120,14 @@ def base_requests(max_len):
     return out
 
 
-class Planned:
-    """Device buffers of one capacity (nreq, max_len); run() as often as wanted."""
-
-    def __init__(self, w: World, nreq, max_len, table=None):
-        torch, D = w.torch, w.D
-        self.w, self.nreq, self.max_len = w, nreq, max_len
-        self.table = table or w.table
-        self.stride = (max_len + 15) // 16 * 16 + 16
-        self.rs = torch.zeros(nreq, dtype=torch.int32, device="cuda")
-        self.start = torch.zeros(nreq, dtype=torch.int64, device="cuda")
-        self.length = torch.zeros(nreq, dtype=torch.int64, device="cuda")
-        need = D.planned_plain_read_scratch(self.table, nreq, max_len).numel()
-        self.full = torch.full((need + 256,), GUARD, dtype=torch.uint8, device="cuda")
-        self.scratch = self.full[:need]
-        self.content = torch.full((nreq * self.stride + 64,), CANARY, dtype=torch.uint8, device="cuda")
-        self.clen = torch.full((nreq,), -1, dtype=torch.int64, device="cuda")
-        self.status = torch.full((nreq + 8,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-        self.used = torch.full((nreq + 8,), 0x3C3C3C3C, dtype=torch.int32, device="cuda")
-        self.vouch = torch.full((nreq + 8,), 0x69696969, dtype=torch.int32, device="cuda")
-
-    def set(self, reqs):
-        torch = self.w.torch
-        self.rs.copy_(torch.tensor([r[0] for r in reqs], dtype=torch.int32))
-        self.start.copy_(torch.tensor([r[1] for r in reqs], dtype=torch.int64))
-        self.length.copy_(torch.tensor([r[2] for r in reqs], dtype=torch.int64))
-        self.content.fill_(CANARY)
+class Planned(RW.Planned):
+    def scratch_len(self):
+        return self.w.D.planned_plain_read_scratch(self.table, self.nreq, self.max_len).numel()
 
     def enqueue(self, flags=0):
         self.w.D.read_plain_ranges_planned(self.table, self.w.ktab, self.rs, self.start, self.length, self.max_len,
                                            self.content, self.stride, self.clen, self.status, self.used, self.vouch,
                                            self.scratch, flags)
-
-    def result(self) -> Got:
-        torch, n = self.w.torch, self.nreq
-        torch.cuda.synchronize()
-        assert (self.full[self.scratch.numel():] == GUARD).all().item(), "bytes behind scratch_len were written"
-        assert (self.status[n:] == 0x5A5A5A5A).all().item() and (self.used[n:] == 0x3C3C3C3C).all().item()
-        assert (self.vouch[n:] == 0x69696969).all().item()
-        got = Got(self.status[:n].cpu().numpy(), self.used[:n].cpu().numpy(), self.vouch[:n].cpu().numpy(),
-                  self.clen.cpu().numpy().tolist(), self.content.cpu().numpy())
-        _check_canary(got.content, got.clen, self.stride)
-        return got
-
-    def run(self, reqs, flags=0) -> Got:
-        self.set(reqs)
-        self.enqueue(flags)
-        return self.result()
 
 
 @functools.lru_cache(maxsize=None)
@@ -172,22 +135,13 @@ def _reference(reqs, stride, flags) -> Got:
     w = world()
     torch, D = w.torch, w.D
     n = len(reqs)
-    rs = [0 if r[3] else r[0] for r in reqs]
-    start = [0 if r[3] else r[1] for r in reqs]
-    length = [0 if r[3] else r[2] for r in reqs]
-    coff = [r * stride for r in range(n)]
+    rs, start, length, coff = RW.host_requests(reqs, stride)
     _, _, _, nseg = D.plain_read_layout(w.cls, w.pads, rs, start, length)
     content = torch.full((n * stride + 64,), CANARY, dtype=torch.uint8, device="cuda")
     status, used, vouch = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(3))
     clen = D.read_plain_ranges(w.keys, w.ivs, w.kstat, w.buf, w.off, w.len, w.hashes, w.pads, w.cls, rs, start, length,
                                content, coff, status, used, vouch, D.plain_read_scratch(n, nseg, len(SIZES)), flags=flags)
-    torch.cuda.synchronize()
-    status, used, vouch = status.cpu().numpy(), used.cpu().numpy(), vouch.cpu().numpy()
-    for r, rq in enumerate(reqs):
-        if rq[3]:
-            assert clen[r] == 0
-            status[r], used[r], vouch[r] = 1, 0, 0
-    return Got(status, used, vouch, clen, content.cpu().numpy())
+    return RW.host_result(reqs, clen, content, status, used, vouch)
 
 
 def reference(w: World, reqs, max_len, stride, flags=0) -> Got:

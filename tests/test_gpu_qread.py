@@ -20,29 +20,18 @@ import functools
 import numpy as np
 import pytest
 
+import read_world as RW  # tests/read_world.py (tests/ is on sys.path under pytest)
+from bao_damage import chunk_off
+from read_world import CANARY, Got, assert_equal
+
 pytestmark = pytest.mark.gpu
 
-CANARY, GUARD = 0xC7, 0x5B
 SO = 56
 # objects 0..5 intact; 6 described with a chunk_len that does not fit; 7..10 damaged
 SIZES = [1, 1000, 4096, 8000, 16384, 262044, 4096, 4000, 4000, 4096, 4096]
 MISFIT, FLIPPED, FIVE, PARENT, CONTRA = 6, 7, 8, 9, 10
 SHARD = [1024, 1024, 1024, 2048, 4096, 65536, 1024, 1024, 1024, 1024, 1024]
 REFUSED = 1
-
-
-def chunk_off(i, N):
-    """Stream offset of chunk i of a bao stream of N full chunks (pre-order)."""
-    off, lo, cnt = 8, 0, N
-    while cnt > 1:
-        off += 64
-        left = 1 << ((cnt - 1).bit_length() - 1)
-        if i < lo + left:
-            cnt = left
-        else:
-            off += left * 1024 + 64 * (left - 1)
-            lo, cnt = lo + left, cnt - left
-    return off
 
 
 class World:
@@ -119,44 +108,13 @@ def base_requests(max_len):
     return out
 
 
-class Got:
-    def __init__(self, status, used, vouch, clen, content):
-        self.status, self.used, self.vouch, self.clen, self.content = status, used, vouch, clen, content
-
-
-def _check_canary(content, clen, stride):
-    rows = content[:len(clen) * stride].reshape(len(clen), stride)
-    outside = np.arange(stride)[None, :] >= np.asarray(clen)[:, None]
-    assert (rows[outside] == CANARY).all(), "a byte outside [0, content_len) of a slot was written"
-    assert (content[len(clen) * stride:] == CANARY).all()
-
-
-class Planned:
-    """Device buffers of one capacity (nreq, max_len); run() as often as wanted."""
-
+class Planned(RW.Planned):
     def __init__(self, w: World, nreq, max_len, vouched, table=None):
-        torch, D = w.torch, w.D
-        self.w, self.nreq, self.max_len, self.vouched = w, nreq, max_len, vouched
-        self.table = table or w.table
-        self.stride = (max_len + 15) // 16 * 16 + 16
-        self.rs = torch.zeros(nreq, dtype=torch.int32, device="cuda")
-        self.start = torch.zeros(nreq, dtype=torch.int64, device="cuda")
-        self.length = torch.zeros(nreq, dtype=torch.int64, device="cuda")
-        need = D.planned_read_scratch(self.table, nreq, max_len, vouched).numel()
-        self.full = torch.full((need + 256,), GUARD, dtype=torch.uint8, device="cuda")
-        self.scratch = self.full[:need]
-        self.content = torch.full((nreq * self.stride + 64,), CANARY, dtype=torch.uint8, device="cuda")
-        self.clen = torch.full((nreq,), -1, dtype=torch.int64, device="cuda")
-        self.status = torch.full((nreq + 8,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-        self.used = torch.full((nreq + 8,), 0x3C3C3C3C, dtype=torch.int32, device="cuda")
-        self.vouch = torch.full((nreq + 8,), 0x69696969, dtype=torch.int32, device="cuda")
+        self.vouched = vouched
+        super().__init__(w, nreq, max_len, table)
 
-    def set(self, reqs):
-        torch = self.w.torch
-        self.rs.copy_(torch.tensor([r[0] for r in reqs], dtype=torch.int32))
-        self.start.copy_(torch.tensor([r[1] for r in reqs], dtype=torch.int64))
-        self.length.copy_(torch.tensor([r[2] for r in reqs], dtype=torch.int64))
-        self.content.fill_(CANARY)
+    def scratch_len(self):
+        return self.w.D.planned_read_scratch(self.table, self.nreq, self.max_len, self.vouched).numel()
 
     def enqueue(self, flags=0):
         D = self.w.D
@@ -167,33 +125,13 @@ class Planned:
             D.read_ranges_planned(self.table, self.rs, self.start, self.length, self.max_len, self.content, self.stride,
                                   self.clen, self.status, self.used, self.scratch)
 
-    def result(self) -> Got:
-        torch, n = self.w.torch, self.nreq
-        torch.cuda.synchronize()
-        assert (self.full[self.scratch.numel():] == GUARD).all().item(), "bytes behind scratch_len were written"
-        assert (self.status[n:] == 0x5A5A5A5A).all().item() and (self.used[n:] == 0x3C3C3C3C).all().item()
-        assert (self.vouch[n if self.vouched else 0:] == 0x69696969).all().item()
-        got = Got(self.status[:n].cpu().numpy(), self.used[:n].cpu().numpy(),
-                  self.vouch[:n].cpu().numpy() if self.vouched else None, self.clen.cpu().numpy().tolist(),
-                  self.content.cpu().numpy())
-        _check_canary(got.content, got.clen, self.stride)
-        return got
-
-    def run(self, reqs, flags=0) -> Got:
-        self.set(reqs)
-        self.enqueue(flags)
-        return self.result()
-
 
 def reference(w: World, reqs, max_len, stride, vouched, flags=0) -> Got:
     """The host-planned call over the same requests at r * stride; a refused
     request reads an empty range there and has status 1, used 0, vouch 0 here."""
     torch, D = w.torch, w.D
     n = len(reqs)
-    rs = [0 if r[3] else r[0] for r in reqs]
-    start = [0 if r[3] else r[1] for r in reqs]
-    length = [0 if r[3] else r[2] for r in reqs]
-    coff = [r * stride for r in range(n)]
+    rs, start, length, coff = RW.host_requests(reqs, stride)
     _, _, _, nseg = D.read_layout(w.cls, w.pads, rs, start, length, 16)
     content = torch.full((n * stride + 64,), CANARY, dtype=torch.uint8, device="cuda")
     status = torch.zeros(n, dtype=torch.int32, device="cuda")
@@ -205,26 +143,7 @@ def reference(w: World, reqs, max_len, stride, vouched, flags=0) -> Got:
     else:
         clen = D.read_ranges(w.buf, w.off, w.len, w.hashes, w.pads, w.cls, rs, start, length, content, coff, status, used,
                              D.read_scratch(n, nseg))
-    torch.cuda.synchronize()
-    status, used, vouch = status.cpu().numpy(), used.cpu().numpy(), vouch.cpu().numpy()
-    for r, rq in enumerate(reqs):
-        if rq[3]:
-            assert clen[r] == 0
-            status[r], used[r], vouch[r] = 1, 0, 0
-    return Got(status, used, vouch if vouched else None, clen, content.cpu().numpy())
-
-
-def assert_equal(got: Got, want: Got, reqs):
-    assert got.clen == want.clen, [(r, reqs[r], a, b) for r, (a, b) in enumerate(zip(got.clen, want.clen)) if a != b][:8]
-    for name in ("status", "used", "vouch"):
-        a, b = getattr(got, name), getattr(want, name)
-        if b is None:
-            continue
-        bad = [(name, r, reqs[r], int(a[r]), int(b[r])) for r in np.flatnonzero(a != b)[:8]]
-        assert not bad, bad
-    if not np.array_equal(got.content, want.content):
-        at = int(np.flatnonzero(got.content != want.content)[0])
-        raise AssertionError(f"content differs at byte {at}")
+    return RW.host_result(reqs, clen, content, status, used, vouch if vouched else None)
 
 
 def _requests(nreq, max_len):

@@ -17,6 +17,7 @@ import math
 import numpy as np
 import pytest
 
+from bao_damage import chunk_off  # tests/bao_damage.py (tests/ is on sys.path under pytest)
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -155,17 +156,6 @@ def _ceil_log2(x):
     return 0 if x <= 1 else (x - 1).bit_length()
 
 
-def _chunk_off(i, N):
-    """stream offset of chunk i of N (pre-order: 8-byte header, parents in front of their subtrees)"""
-    before, cnt, lvl = 0, N, 1
-    while cnt > 1:
-        before += min((i + (1 << lvl) - 1) >> lvl, cnt // 2)
-        cnt, lvl = (cnt + 1) // 2, lvl + 1
-    cl = _ceil_log2(N - i)
-    at = cl if i == 0 else min((i & -i).bit_length() - 1, cl)
-    return 8 + 1024 * i + 64 * (before + at)
-
-
 def _spots(bao_n):
     """name -> byte offset in a stream of bao_n content bytes (None: no such node)"""
     N = max(1, (bao_n + 1023) // 1024)
@@ -173,9 +163,9 @@ def _spots(bao_n):
     return {
         "header": 3,
         "root": 8 + 17 if N > 1 else None,
-        "chunk0": _chunk_off(0, N) if bao_n else None,
+        "chunk0": chunk_off(0, N) if bao_n else None,
         "last_chunk": 8 + bao_n + 64 * (N - 1) - 1 if bao_n else None,
-        "level1_group0": _chunk_off(0, N) - 64 + 40 if N > 1 else None,
+        "level1_group0": chunk_off(0, N) - 64 + 40 if N > 1 else None,
         # the level-7 node over groups 0 and 1 on the left spine, where it is not the root itself
         "above_groups": 8 + 64 * (root_level - 7) + 33 if root_level > 7 else None,
         "hash": -1,

@@ -14,19 +14,12 @@ import pytest
 import torch
 
 import snap_data as SD
+from read_world import dev, up16
 
 pytestmark = pytest.mark.gpu
 
 OK, TOO_SMALL, BAO, MANY, SNAP, ECIES = 0, 2, 5, 11, 16, 17
 SECRET = bytes(range(1, 33))
-
-
-def up16(x: int) -> int:
-    return (x + 15) // 16 * 16
-
-
-def dev(a) -> torch.Tensor:
-    return torch.from_numpy(np.array(a, dtype=np.uint8)).cuda()   # (a writable copy)
 
 
 def host_snap(data: bytes) -> bytes:

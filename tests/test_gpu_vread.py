@@ -43,19 +43,14 @@ class VWant(NamedTuple):
     classes: tuple
 
 
-@functools.lru_cache(maxsize=None)
-def _chunk_offsets(spc: int):
-    return tuple(nd.off for nd in B.tree_nodes(8192 * spc) if not nd.parent)
-
-
 def _window(stream: bytes, spc: int, shard: int, w0: int, w1: int) -> bytes:
-    off = _chunk_offsets(spc)
+    off = B.chunk_offsets(spc)
     return b"".join(stream[off[shard * spc + c]:off[shard * spc + c] + 1024] for c in range(w0, w1))
 
 
 def _path_holds(st, bad: bytes, p: int, w0: int, w1: int) -> bool:
     fixed = bytearray(bad)
-    off = _chunk_offsets(st.spc)
+    off = B.chunk_offsets(st.spc)
     for c in range(p * st.spc + w0, p * st.spc + w1):
         fixed[off[c]:off[c] + 1024] = st.clean[off[c]:off[c] + 1024]
     start, ln = (p * st.spc + w0) * 1024, (w1 - w0) * 1024
