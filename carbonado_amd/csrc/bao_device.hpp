@@ -187,20 +187,6 @@ __device__ __forceinline__ void b3_compress(uint32_t (&h)[8], const uint32_t (&m
     for (int i = 0; i < 8; ++i) h[i] = v[i] ^ v[i + 8];
 }
 
-// The same with f(r) called after round r (fused_tune: instructions placed
-// between the rounds, e.g. stores spread over a compression).
-template <class F>
-__device__ __forceinline__ void b3_compress_cb(uint32_t (&h)[8], const uint32_t (&m)[16], uint64_t ctr,
-                                               uint32_t blen, uint32_t flags, F &&f) {
-    uint32_t v[16] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7],
-                      IV(0), IV(1), IV(2), IV(3),
-                      (uint32_t)ctr, (uint32_t)(ctr >> 32), blen, flags};
-    b3_round<0>(v, m); f(0); b3_round<1>(v, m); f(1); b3_round<2>(v, m); f(2); b3_round<3>(v, m); f(3);
-    b3_round<4>(v, m); f(4); b3_round<5>(v, m); f(5); b3_round<6>(v, m); f(6);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = v[i] ^ v[i + 8];
-}
-
 __device__ __forceinline__ void b3_parent(const uint32_t (&l)[8], const uint32_t (&r)[8], bool root,
                                           uint32_t (&out)[8]) {
     uint32_t m[16];
@@ -403,26 +389,22 @@ __host__ __device__ constexpr int ilog2(int x) { return x <= 1 ? 0 : 1 + ilog2(x
 // wave through LDS (coalesced 16-B loads, 8 lanes = one 128-B line), with the
 // next step's loads prefetched into registers while the lane compresses.
 // SP (stream path, MODE 0): 0 = aligned pieces re-read from the LDS rows;
-// 1 = pieces built in registers from the loaded data (DPP neighbour exchange);
-// 2 = diagnostic for tools/bao_tune only (128-B aligned bases, wrong layout);
 // 3 = rows hold two steps (ping-pong) and every step stores one whole aligned
 //     128-B line of the stream per chunk (plus the head at step 0 and the
-//     tail at step 7), so no line is written in two halves.
-// SE 2 / 3: diagnostics for tools/bao_tune (LDS reads without the stores /
-// stores without the LDS reads; wrong output).  SE 6 (MODE 1, diagnostic,
-// wrong output): every chunk read from its slot rounded down to a 128-B
-// line, so no memory line is shared by two owners and fetched twice, and no
-// level-1 node is read: verify-decode's time without its duplicated
-// border-line fetches, at the product's occupancy.
-// SU: unroll of the SP 3 store loop; SE: issue the SP 3 stores before (1) or
-// after (0) the next step's prefetch loads.
-// XG 1: XCD-grouped block order (block b runs logical block (b % 8) * (B/8) + b/8,
-// so each XCD sweeps one contiguous eighth of the batch; B % 8 == 0 only).
-// DQ: persistent grid, wave tasks from the run queue a.queue (zero at launch).
+//     tail at step 7), so no line is written in two halves; the stores are
+//     issued after the next step's prefetch loads.
+// SU: unroll of the SP 3 store loop.
+// DQ: persistent grid, wave tasks from the run queue a.queue (zero at launch);
+// otherwise one wave per task in XCD-grouped block order (block b runs
+// logical block (b % 8) * (B/8) + b/8, so each XCD sweeps one contiguous
+// eighth of the batch; B % 8 == 0 only): +0.9-1.8 % on encode / decode /
+// in-place over the plain order (tools/bao_tune, r1x).
 // This is the kernel body; ChunkKernel below names the kernel launched for a
-// configuration.
-template <int MODE, int CPL, bool NTS, int SP = 0, int SU = 1, int SE = 0, int XG = 0, bool DQ = false>
+// configuration.  The stream paths, store orders and diagnostics it once
+// carried are in profiles/NOT_KEPT.md.
+template <int MODE, int CPL, bool NTS, int SP = 0, int SU = 1, bool DQ = false>
 __device__ __forceinline__ void bao_chunk_body(const ChunkArgs &a) {
+    static_assert(SP == 0 || SP == 3, "stream path");
     constexpr int LOG = ilog2(CPL);
     constexpr int NSTEP = 8 * CPL;
     // SP 3: [pad 4 | step-parity-0 data 32 | step-parity-1 data 32] words per row
@@ -436,7 +418,7 @@ __device__ __forceinline__ void bao_chunk_body(const ChunkArgs &a) {
     const uint64_t span = 64ull * CPL;
     const uint64_t tpo = (a.N + span - 1) / span;
     uint64_t blk = blockIdx.x;
-    if (!DQ && XG && (gridDim.x & 7) == 0) blk = (blk & 7) * (gridDim.x >> 3) + (blk >> 3);
+    if (!DQ && (gridDim.x & 7) == 0) blk = (blk & 7) * (gridDim.x >> 3) + (blk >> 3);
     // DQ: wave tasks from a run queue (one atomic per task, lane 0; vector
     // memory), persistent grid: the slower XCDs take fewer tasks.  Otherwise
     // one task per wave of the grid.
@@ -487,12 +469,6 @@ __device__ __forceinline__ void bao_chunk_body(const ChunkArgs &a) {
                         for (int t = 0; t < 8; ++t) soff_t[t] = soff[j & 1][wave][t * 8 + (lane >> 3)];
                     }
                     const uint8_t *b = ib + s * 128 + (lane & 7) * 16;
-                    if constexpr (SE == 6) {  // diagnostic: each chunk read from its slot rounded down to 128 B
-    #pragma unroll
-                        for (int t = 0; t < 8; ++t)
-                            v[t] = *reinterpret_cast<const u32x4 *>(b + (soff_t[t] & ~(uint64_t)127));
-                        return;
-                    }
     #pragma unroll
                     for (int t = 0; t < 8; ++t) v[t] = load16_a8(b + soff_t[t]);
                 }
@@ -597,51 +573,10 @@ __device__ __forceinline__ void bao_chunk_body(const ChunkArgs &a) {
             }
         };
 
-        // encode, SP 1: straight from the loaded registers.  Lane g of a chunk's
-        // 8-lane group holds chunk bytes [128s+16g, +16) at stream offset 8 (mod 16);
-        // it stores the ALIGNED 16 B [128s+16g+8, +16) = its upper half + the next
-        // lane's lower half (DPP row_shl:1), lane 0 adds the 8-B head of the step
-        // and lane 7 the 8-B tail, so a step needs no bytes of its neighbours.
-        auto stream_regs = [&](int g, const u32x4 (&v)[8]) {
-            const int j = g >> 3, s = g & 7, gl = lane & 7;
-            uint64_t bo[8];
-    #pragma unroll
-            for (int t = 0; t < 8; ++t) bo[t] = soff[j & 1][wave][t * 8 + (lane >> 3)];
-    #pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const uint32_t nx = __builtin_amdgcn_update_dpp(0u, v[t].x, 0x101, 0xF, 0xF, false);
-                const uint32_t ny = __builtin_amdgcn_update_dpp(0u, v[t].y, 0x101, 0xF, 0xF, false);
-                const int cc = t * 8 + (lane >> 3);
-                const uint64_t ci = c0 + (uint64_t)cc * CPL + j;
-                if (!(wave_on && ci < a.N)) continue;
-                const uint64_t rem = a.n - ci * 1024;
-                const uint32_t clen = rem < 1024 ? (uint32_t)rem : 1024u;
-                if (SP == 2) {
-                    uint8_t *q = ob + (bo[t] & ~127ull) + 128 * s + 16 * gl;
-                    if (clen == 1024) *reinterpret_cast<u32x4 *>(q) = v[t];
-                    continue;
-                }
-                uint8_t *p = ob + bo[t] + 128 * s + 16 * gl;
-                if (clen == 1024) {
-                    if (gl < 7) {
-                        const u32x4 o = {v[t].z, v[t].w, nx, ny};
-                        if (NTS) __builtin_nontemporal_store(o, reinterpret_cast<u32x4 *>(p + 8));
-                        else *reinterpret_cast<u32x4 *>(p + 8) = o;
-                    }
-                    if (gl == 0 || gl == 7)
-                        store8<NTS>(gl == 0 ? p : p + 8, gl == 0 ? u32x2{v[t].x, v[t].y} : u32x2{v[t].z, v[t].w});
-                } else {  // short last chunk of the object
-                    const uint32_t cb = 128u * s + 16u * gl;
-                    if (cb < clen) store16_partial(p, v[t], clen - cb);
-                }
-            }
-        };
-
         // encode, SP 3: chunk bytes x live in the row at word dofs(x >> 7) + (x & 127) / 4.
         // The stream lines (128-B aligned in stream space) inside a chunk start at
         // chunk byte d + 128 t, d = (-base) mod 128; at step s the line ending at
         // d + 128 s is complete (its first part is in the other half of the row).
-        uint32_t diag = 0;  // SE 2 diagnostic sink
         uint8_t *lsp[8];  // SP 3 fast path: stream address and line phase of chunk t*8 + lane/8, per round
         uint32_t ldd[8];
         auto stream_lines = [&](int g) {
@@ -667,25 +602,8 @@ __device__ __forceinline__ void bao_chunk_body(const ChunkArgs &a) {
                     const uint32_t *row = st + (t * 8 + (lane >> 3)) * RW;
                     if (s >= 1) {  // the whole line [d + 128(s-1), d + 128 s)
                         const uint32_t x = d + 128u * (s - 1) + 16u * gl;
-                        if constexpr (SE == 3) {  // diagnostic (tools/bao_tune): the stores without the LDS reads
-                            *reinterpret_cast<u32x4 *>(sp + x) = u32x4{x, d, x, d};
-                            continue;
-                        }
-                        if constexpr (SE == 4) {  // diagnostic: as 3, every wave rewriting the same 8 KiB (L2 hits)
-                            *reinterpret_cast<u32x4 *>(ob + t * 1024 + lane * 16) = u32x4{x, d, x, d};
-                            continue;
-                        }
-                        if constexpr (SE == 5) {  // diagnostic: as 3, half the stores
-                            if (t & 1) continue;
-                            *reinterpret_cast<u32x4 *>(sp + x) = u32x4{x, d, x, d};
-                            continue;
-                        }
                         const u32x2 lo = piece(row, x), hi = piece(row, x + 8);
                         const u32x4 v = {lo.x, lo.y, hi.x, hi.y};
-                        if constexpr (SE == 2) {  // diagnostic: the LDS reads without the stores
-                            diag ^= v.x ^ v.w;
-                            continue;
-                        }
                         if (NTS) __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(sp + x));
                         else *reinterpret_cast<u32x4 *>(sp + x) = v;
                     } else {  // head [0, d)
@@ -767,7 +685,7 @@ __device__ __forceinline__ void bao_chunk_body(const ChunkArgs &a) {
         // step-0 loads fetch anyway.  Read it now, with them, instead of at
         // the pair's end (step 15), when those lines have long left L2 and
         // are fetched again (decode read 1.18x its stream).
-        constexpr bool PN = MODE == 1 && CPL == 2 && BAO_DEC_PREFETCH && SE != 6;
+        constexpr bool PN = MODE == 1 && CPL == 2 && BAO_DEC_PREFETCH;
         u32x4 pnode[4];
         if (PN && nmine == 2) {
             const uint8_t *np = ib + my_off - 64;
@@ -787,17 +705,15 @@ __device__ __forceinline__ void bao_chunk_body(const ChunkArgs &a) {
                 *reinterpret_cast<u32x4 *>(row + dofs(s) + (lane & 7) * 4) = pre[t];
             }
             if (MODE == 1 && ob) content_step(g, pre);
-            if (MODE == 0 && ob && (SP == 1 || SP == 2)) stream_regs(g, pre);
             if (s == 7 && j + 1 < CPL) {  // stream offset of my next chunk, for the loads issued below
                 const uint64_t ni = lb + j + 1;
                 if ((uint64_t)(j + 1) < nmine) my_off += 1024 + 64 * (uint64_t)parents_at(ni, a.N);
                 soff[(j + 1) & 1][wave][lane] = my_off;
             }
             wave_sync();
-            if (MODE == 0 && ob && SP == 3 && SE == 1) stream_lines(g);
             if (g + 1 < NSTEP) load_step(g + 1, pre);  // in flight during the compressions
             if (MODE == 0 && ob && SP == 0) stream_step(wave, g);
-            if (MODE == 0 && ob && SP == 3 && SE != 1) stream_lines(g);
+            if (MODE == 0 && ob && SP == 3) stream_lines(g);
 
             const uint64_t i = lb + j;
             const bool mine = (uint64_t)j < nmine;
@@ -888,8 +804,7 @@ __device__ __forceinline__ void bao_chunk_body(const ChunkArgs &a) {
                 for (int w = 0; w < 8; ++w) h[w] = IV(w);
             }
         }
-        if (MODE == 1 && !ok && SE != 6) flag_mismatch(a.status, obj);
-        if (SE == 2 && diag == 0x9E3779B9u && ob) ob[0] = 0;  // keep the diagnostic's reads alive
+        if (MODE == 1 && !ok) flag_mismatch(a.status, obj);
         if (!DQ) break;
     }
     if (DQ && lane == 0) {  // the last wave out leaves the queue zero for the next launch

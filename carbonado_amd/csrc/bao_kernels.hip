@@ -56,8 +56,6 @@ constexpr bool BAO_NTS = false;
 #endif
 constexpr bool BAO_DEC_NTS = BAO_DEC_NTS_DEF;
 constexpr int BAO_SP = 3;
-// XCD-grouped block order: +0.9-1.8 % on encode / decode / in-place (tools/bao_tune, r1x)
-constexpr int BAO_XG = 1;
 // SP 3 store loop fully unrolled over the 8 chunk groups: +0.6-0.9 % (tools/bao_tune, r1x)
 constexpr int BAO_SU = 8;
 // Persistent grid with wave tasks from the stream's run queue: the XCDs do
@@ -74,17 +72,17 @@ constexpr bool BAO_DQ = true;
 // batch of 2^31 wave tasks or more).
 #define CHIP_K3(NAME, MODE, CPL, NTS, SP, SU)                                                   \
     __global__ __launch_bounds__(K3_TPB) void NAME(ChunkArgs a) {                              \
-        bao_chunk_body<MODE, CPL, NTS, SP, SU, 0, BAO_XG, BAO_DQ>(a);                          \
+        bao_chunk_body<MODE, CPL, NTS, SP, SU, BAO_DQ>(a);                                     \
     }                                                                                         \
     __global__ __launch_bounds__(K3_TPB) void NAME##_static(ChunkArgs a) {                     \
-        bao_chunk_body<MODE, CPL, NTS, SP, SU, 0, BAO_XG, false>(a);                           \
+        bao_chunk_body<MODE, CPL, NTS, SP, SU, false>(a);                                      \
     }                                                                                         \
     template <>                                                                               \
-    struct ChunkKernel<MODE, CPL, NTS, SP, SU, 0, BAO_XG, true> {                             \
+    struct ChunkKernel<MODE, CPL, NTS, SP, SU, true> {                                        \
         static constexpr void (*fn)(ChunkArgs) = NAME;                                        \
     };                                                                                        \
     template <>                                                                               \
-    struct ChunkKernel<MODE, CPL, NTS, SP, SU, 0, BAO_XG, false> {                            \
+    struct ChunkKernel<MODE, CPL, NTS, SP, SU, false> {                                       \
         static constexpr void (*fn)(ChunkArgs) = NAME##_static;                               \
     };
 namespace bao {
@@ -101,8 +99,8 @@ template <int MODE>
 hipError_t run_bao(const uint8_t *d_in, uint64_t in_stride, uint64_t n, uint64_t count,
                    uint8_t *d_out, uint64_t out_stride, uint8_t *d_hash, uint32_t *d_status,
                    void *d_scratch, hipStream_t stream) {
-    return run_bao_t<MODE, BAO_CPL, MODE == 1 ? BAO_DEC_NTS : BAO_NTS, MODE == 0 ? BAO_SP : 0, MODE == 0 ? BAO_SU : 1, 0,
-                     BAO_XG, BAO_DQ>(
+    return run_bao_t<MODE, BAO_CPL, MODE == 1 ? BAO_DEC_NTS : BAO_NTS, MODE == 0 ? BAO_SP : 0, MODE == 0 ? BAO_SU : 1,
+                     BAO_DQ>(
         d_in, in_stride, n, count, d_out, out_stride, d_hash, d_status, d_scratch, stream);
 }
 
@@ -140,9 +138,9 @@ hipError_t bao_decode_prefix_dev(const uint8_t *d_in, uint64_t in_stride, uint64
     if (small_ok(n, count))
         return small_bao_decode_dev(d_in, in_stride, n, count, d_hash, d_out, out_stride, std::min(out_limit, n),
                                     d_status, stream);
-    return run_bao_t<1, BAO_CPL, BAO_DEC_NTS, 0, 1, 0, BAO_XG, BAO_DQ>(d_in, in_stride, n, count, d_out, out_stride,
-                                                          const_cast<uint8_t *>(d_hash), d_status, d_scratch, stream,
-                                                          0, out_limit);
+    return run_bao_t<1, BAO_CPL, BAO_DEC_NTS, 0, 1, BAO_DQ>(d_in, in_stride, n, count, d_out, out_stride,
+                                                            const_cast<uint8_t *>(d_hash), d_status, d_scratch, stream,
+                                                            0, out_limit);
 }
 
 hipError_t bao_node_check(const uint8_t *d_stream, uint64_t stride, uint64_t n, uint64_t count,
@@ -201,8 +199,8 @@ hipError_t bao_encode_inplace_dev(uint8_t *d_stream, uint64_t stride, uint64_t n
     // three tree levels fold in registers (tools/bao_tune: 3.15 vs 3.39 ms
     // for CPL 2 on 256 x 32 MiB; fewer K4 launches).  Scratch sized for
     // BAO_CPL covers it (N/8 <= N/2 level nodes).
-    return run_bao_t<3, 8, BAO_NTS, 0, 1, 0, BAO_XG, BAO_DQ>(d_stream, stride, n, count, d_stream, stride, d_hash,
-                                                             nullptr, d_scratch, stream);
+    return run_bao_t<3, 8, BAO_NTS, 0, 1, BAO_DQ>(d_stream, stride, n, count, d_stream, stride, d_hash, nullptr,
+                                                  d_scratch, stream);
 }
 
 namespace {

@@ -59,20 +59,19 @@ struct FusedArgs {
     const uint32_t *table;          // [4][256] packed parity products (4 parity rows per dword)
     const uint64_t *coff;           // [N] stream offset of each chunk (bao_chunk_table)
     uint8_t *cv;                    // level-0 CVs [count][N], or level-3 CVs [count][cvs] (FULL)
-    uint32_t *queue;                // block queue (DQ): [0] next block, [32] waves done; zero at launch
+    uint32_t *queue;                // block queue: [0] next block, [32] waves done; zero at launch
     uint64_t cvs;                   // FULL: level-3 CVs per object = ceil(N / 8)
-    uint8_t *cv3;                   // RT: level-3 CVs [count][cvs] (the groups the waves complete)
 };
 
-// RT (general path, runs of RT blocks): whether the aligned 8-chunk group g
-// of a stream of 8 shards of `cols` chunk-columns each is completed inside a
-// wave.  The group's chunks must lie in one shard t, at columns [u0, u0 + 8);
-// its last column lies in block (u0 + 7) / 8, which completes it; the part
-// before that block (u0 % 8 != 0: rows whose shard starts off the 8-chunk
-// grid) lies in the previous block, processed by the same wave just before
-// unless the completing block starts a run.  Everything else (groups across
-// two shards, groups across a run boundary) is completed by the level-1-3
-// pass from the level-0 CVs the waves store for exactly those chunks.
+// Whether the aligned 8-chunk group g of a stream of 8 shards of `cols`
+// chunk-columns each would be completed inside a K13 wave that takes its
+// blocks in runs of rt > 0 consecutive blocks of one object (K13's run mode,
+// not kept: profiles/NOT_KEPT.md).  The group's chunks must lie in one shard
+// t, at columns [u0, u0 + 8); its last column lies in block (u0 + 7) / 8,
+// which completes it; the part before that block (u0 % 8 != 0: rows whose
+// shard starts off the 8-chunk grid) lies in the previous block, processed by
+// the same wave just before unless the completing block starts a run.  Only
+// bao_levels123_lds_kernel asks, and only when its rt argument is not 0.
 __host__ __device__ inline bool group_in_wave(uint64_t g, uint64_t cols, uint64_t bpo, uint64_t rt) {
     const uint64_t c0 = 8 * g, t = c0 / cols;
     if ((c0 + 7) / cols != t) return false;
@@ -109,10 +108,9 @@ __device__ __forceinline__ uint32_t gf_pair(uint32_t x, int hi, uint32_t tb2) {
     return t;
 }
 
-template <bool NT>
+// a whole-line piece of the stream: nontemporal, the lines are not read back
 __device__ __forceinline__ void st16(uint8_t *p, u32x4 v) {
-    if (NT) __builtin_nontemporal_store(v, bao::glb(reinterpret_cast<u32x4 *>(p)));
-    else *bao::glb(reinterpret_cast<u32x4 *>(p)) = v;
+    __builtin_nontemporal_store(v, bao::glb(reinterpret_cast<u32x4 *>(p)));
 }
 
 // Levels 1-3 of the tree inside the wave, pipelined over blocks.  With
@@ -126,7 +124,6 @@ __device__ __forceinline__ void st16(uint8_t *p, u32x4 v) {
 // compression.  Each parent node (l || r) is written at its stream slot —
 // the node with leftmost chunk s at level k sits 64 k bytes before chunk s —
 // and the level-3 CVs go to `cv` [count][N/8] for the parent kernels.
-template <bool NT>
 struct Tree {
     uint32_t pr[8];   // my last parent CV (roles 1 and 2)
     uint8_t *node;    // ... its node slot
@@ -134,7 +131,6 @@ struct Tree {
     bool ok = false;  // ... valid
     int lane;
     uint8_t *cv;
-    bool wr = true;  // write the nodes (false: tools/fused_tune diagnostic DG 11)
     __device__ Tree(int l, uint8_t *c) : node(nullptr), cvi(0), lane(l), cv(c) {
 #pragma unroll
         for (int w = 0; w < 8; ++w) pr[w] = 0u;
@@ -162,7 +158,7 @@ struct Tree {
         if (act) {
             uint32_t p[8];
             bao::b3_parent(l, r, false, p);
-            if (wr) bao::node_io<0, NT>(my, l, r);
+            bao::node_io<0, true>(my, l, r);
             if (r3) {
                 bao::store_cv(cv + (mc / 8) * 32, p);
             } else {
@@ -176,48 +172,35 @@ struct Tree {
     }
 };
 
-// DG: diagnostics for tools/fused_tune (wrong output): 1 = no line stores,
-// 2 = no hashing, 3 = no GF (rows get the data shards only), 4 = neither
-// stores nor hashing, 5 = every chunk's lines 128-B aligned (no partial
-// lines), 6 = 5 without hashing, 7 = the line stores' LDS reads without the
-// stores, 8 = the whole-line stores aimed at 8 KiB per wave (L2 hits),
-// 10 = GF table lookups without bank conflicts (wrong products); read-traffic
-// attribution (tools/k13_fetch): 11 = FULL without the in-wave tree's node
-// stores, 12 = general with the level 1-3 node slots in front of each chunk
-// zero-filled at step 0 (lines whole inside the kernel), 13 = general without
-// the level-0 CV stores, 14 = general with the level-0 CVs in a block-padded
-// layout [obj][shard][8 bpo] (each block's 8 CVs of a shard = one aligned
-// 256-B run).
+// The kernel body.  Per step: the GF role fills the rows; the hash role's
+// first compression; the store role's whole lines (their LDS reads issued
+// before that compression, the line stores nontemporal) and, after them, the next
+// step's loads; the second compression.  The waves of a persistent grid take
+// their blocks from the queue a.queue, so waves on slower XCDs take fewer.
 // FULL: cols % 8 == 0 and no zfec padding (valid >= 4 C): every block is 8
 // whole columns of plain loads, levels 1-3 run in the wave (Tree) and `cv`
-// receives level-3 CVs; otherwise lanes are predicated and `cv` receives the
-// level-0 CVs.  ORD 1 places the line stores between the step's two
-// compressions (their LDS reads issued before the first) and the next step's
-// loads after them; ORD 2 issues those loads first, as soon as the step's
-// rows are written.
+// receives level-3 CVs; otherwise lanes are predicated, `cv` receives the
+// level-0 CVs, and both compressions' message words of a step are read from
+// the rows at once, before the store role's piece reads, so the second
+// compression's LDS reads land while the first one runs (FULL reads each
+// right before its compression; it measured no gain from reading ahead).
 // KIND 0: encode() Zfec|Bao (zfec 4-of-8, then bao of the 8 shards); KIND 1:
 // bao of the content itself (encoding::bao, encode() level 4; FULL only: the
-// launch covers the whole 64-chunk blocks, bao_tail_kernel the rest).  KIND 1's block is 64 consecutive chunks (row / hash lane
-// L = chunk ub + L), loaded 8 x 16 B per lane per step instead of computed.
-// MP 1: both compressions' message words of a step are read from the rows at
-// once, before the store role's piece reads, so the second compression's LDS
-// reads land while the first one runs (MP 0: each read right before its
-// compression, its latency exposed).
-// SS 1: the step's 8 whole-line stores issued two after each of the first
-// four rounds of the first compression (scheduling barriers around them)
-// instead of as one burst between the compressions.
+// launch covers the whole 64-chunk blocks, bao_tail_kernel the rest).  KIND
+// 1's block is 64 consecutive chunks (row / hash lane L = chunk ub + L),
+// loaded 8 x 16 B per lane per step instead of computed.
 // O32: every object's input and stream are < 4 GiB (the host checks), so
 // loads and stores address them as the wave's object base (SGPRs) plus a
 // 32-bit per-lane offset: global_load/store with saddr, no 64-bit VALU adds
-// per access.  GFP 1: table addresses through gf_pair.
-// WPG: waves per workgroup (FW; tools/fused_tune runs 4 = one wave per SIMD
-// to measure the kernel's sensitivity to occupancy).
+// per access.  GFP 1: table addresses through gf_pair.  NTL: nontemporal
+// input loads.
 //
-// This is the kernel body; the product's launches are the few configurations
-// fused_kernels.hip wraps in kernels of their own (zfec_bao_fused_kernel_full,
-// _general, bao_content_fused_kernel), the tuner's are tools/fused_variants.hpp's.
-template <bool NT, bool FULL, int ORD = 1, int DG = 0, int KIND = 0, bool DQ = true, int MP = 0, int SS = 0,
-          bool O32 = false, int GFP = 0, int WPG = FW, bool NTL = false, int PRIO = 0, int RT = 0>
+// The product's launches are the few configurations fused_kernels.hip wraps
+// in kernels of their own (zfec_bao_fused_kernel_full, _general,
+// bao_content_fused_kernel), the tuner's are tools/fused_variants.hpp's.
+// The load orders, store schedules, priorities, run mode and diagnostics this
+// body once carried are in profiles/NOT_KEPT.md.
+template <bool FULL, int KIND = 0, bool O32 = false, int GFP = 0, bool NTL = false>
 __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
     static_assert(KIND == 0 || FULL, "content bao: FULL blocks only");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -226,7 +209,7 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
     const uint64_t TS = KIND ? 8 : a.cols;   // chunk index step between the 8 lane groups
     if (KIND == 0) {  // table: lds[x][s][r] = T_s[x], FR replicas
         uint32_t *dst = reinterpret_cast<uint32_t *>(lds);
-        for (int i = threadIdx.x; i < 256 * 4 * FR; i += 64 * WPG) {
+        for (int i = threadIdx.x; i < 256 * 4 * FR; i += FTPB) {
             const int x = i / (4 * FR);
             const int s = (i - x * (4 * FR)) / FR;
             dst[i] = a.table[s * 256 + x];
@@ -235,9 +218,7 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    // WPG > FW (tools/fused_tune occupancy diagnostic only, wrong output): the
-    // extra waves share the first waves' rows, the LDS holds FW waves' rows
-    uint32_t *rows = reinterpret_cast<uint32_t *>(lds + TAB_BYTES) + (WPG > FW ? wave % FW : wave) * 64 * RW;
+    uint32_t *rows = reinterpret_cast<uint32_t *>(lds + TAB_BYTES) + wave * 64 * RW;
     const int rep = lane % FR, grp = (lane & 31) / FR;
     uint32_t tb[4], tb2[4];
     uint64_t ioff[4];
@@ -249,7 +230,7 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
     }
     const int gl = lane & 7, cu = lane >> 3;
     const uint64_t total = a.count * a.bpo;
-    const uint64_t GW = (uint64_t)gridDim.x * WPG;
+    const uint32_t waves = gridDim.x * (uint32_t)FW;  // of the whole grid
 
     // Loads of a step.  A block whose input columns all lie below `valid`
     // (every block of an object without zfec padding) takes plain loads whose
@@ -290,51 +271,20 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
         }
     };
 
-    // RT > 0 (general path): the blocks come in runs of RT consecutive blocks of
-    // one object (the queue hands out runs), so a wave holds each block's
-    // predecessor and completes levels 1-3 of the aligned groups that start
-    // in it (group_in_wave), as the FULL path does for all groups.  A tuner
-    // variant (tools/k13_fetch), not shipped: 13 % slower kernel than RT = 0
-    // at the level-15 shard length (profiles/r10e_session)
-    constexpr bool RUNS = !FULL && RT > 0 && KIND == 0;
-    Tree<NT> tree(lane, RUNS ? a.cv3 : a.cv);
-    tree.wr = DG != 11;
-    // Blocks: DQ takes them from a queue (one atomic per block and wave, lane
-    // 0, vector memory), so waves on slower XCDs simply take fewer; otherwise
-    // a static stride of GW.  The next block is known before the current one
-    // starts, for its first loads at step 7.
+    Tree tree(lane, a.cv);
+    // Blocks come from a queue (one atomic per block and wave, lane 0, vector
+    // memory), so waves on slower XCDs simply take fewer.  The next block is
+    // known before the current one starts, for its first loads at step 7.
     auto grab = [&]() -> uint64_t {
         uint32_t b = 0;
         if (lane == 0) b = atomicAdd(a.queue, 1u);
         return (uint64_t)__builtin_amdgcn_readfirstlane(b);
     };
-    const uint64_t rpo = RUNS ? (a.bpo + RT - 1) / RT : 1;  // runs per object
-    uint64_t run_last = 0, srun = (uint64_t)blockIdx.x * WPG + wave;
-    auto run_first = [&](uint64_t r) -> uint64_t {  // first block of run r (total: none left)
-        if (r >= a.count * rpo) return total;
-        const uint64_t o = r / rpo, b0 = o * a.bpo + (r - o * rpo) * RT;
-        run_last = (b0 + RT < (o + 1) * a.bpo ? b0 + RT : (o + 1) * a.bpo) - 1;
-        return b0;
-    };
-    auto next_block = [&](uint64_t b) -> uint64_t {
-        if (RUNS) {
-            if (b < run_last) return b + 1;
-            if (!DQ) srun += GW;
-            return run_first(DQ ? grab() : srun);
-        }
-        return DQ ? grab() : b + GW;
-    };
-    uint64_t blk = RUNS ? run_first(DQ ? grab() : srun) : DQ ? grab() : (uint64_t)blockIdx.x * WPG + wave;
-    uint32_t hp[8];  // RUNS: the previous block's chunk CVs
-#pragma unroll
-    for (int w = 0; w < 8; ++w) hp[w] = 0u;
-    u32x4 v[NV], v2[NV];  // this step's loads; ORD 3: the next step's too
-    if (blk < total) {
-        load_step(blk, 0, v);
-        if (ORD == 3) load_step(blk, 1, v2);
-    }
+    uint64_t blk = grab();
+    u32x4 v[NV];  // this step's loads
+    if (blk < total) load_step(blk, 0, v);
     for (uint64_t nxt; blk < total; blk = nxt) {
-        nxt = next_block(blk);
+        nxt = grab();
         const uint64_t obj = blk / a.bpo, ub = (blk - obj * a.bpo) * BW;
         uint8_t *ob = a.out + obj * a.out_stride;
         if (ub == 0 && lane == 0)  // u64 LE content length
@@ -355,8 +305,7 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 uint8_t *p = ob + co[t];
-                if (DG == 5 || DG == 6) p = reinterpret_cast<uint8_t *>((uintptr_t)p & ~(uintptr_t)127);
-                ldd[t] = (DG == 5 || DG == 6) ? 0u : (uint32_t)(-(uintptr_t)p) & 127u;
+                ldd[t] = (uint32_t)(-(uintptr_t)p) & 127u;
                 if (O32) lso[t] = (uint32_t)(p - ob);
                 else lsp[t] = p;
             }
@@ -379,9 +328,6 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
         for (int w = 0; w < 8; ++w) h[w] = bao::IV(w);
 
         for (int s = 0; s < 8; ++s) {
-            // PRIO 1 (tools/fused_tune): the GF and store roles at raised wave
-            // priority, the compressions at the base one
-            if (PRIO) __builtin_amdgcn_s_setprio(1);
             // ---- GF role: 8 pieces of 16 B into the rows of chunks (sh, cu) ----
             if (KIND == 1) {  // content: the 8 loaded pieces are the rows' bytes
                 const int wo = dofs(s) + 4 * gl;
@@ -389,38 +335,29 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
                 for (int t = 0; t < NV; ++t) *reinterpret_cast<u32x4 *>(rows + (t * 8 + cu) * RW + wo) = v[t];
             } else {
             uint32_t acc[16];
-            if (DG == 3) {
+            // per output word, the 4 shards' lookups together: independent
+            // LDS reads the compiler can keep in flight (shard-outer order
+            // left it one register for them, an lgkmcnt(0) per lookup)
 #pragma unroll
-                for (int c = 0; c < 16; ++c) acc[c] = zf::comp(v[c & 3], c >> 2);
-            } else {
-                // per output word, the 4 shards' lookups together: independent
-                // LDS reads the compiler can keep in flight (shard-outer order
-                // left it one register for them, an lgkmcnt(0) per lookup)
+            for (int d = 0; d < 4; ++d) {
+                uint32_t x[4], ad[4][4];
 #pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    uint32_t x[4], ad[4][4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        x[j] = zf::comp(v[j], d);
-                        // DG 10 (diagnostic, wrong bytes): lanes l and l + 16 look up
-                        // table rows of opposite parity, so no two lanes of a 32-lane
-                        // half meet on one bank (FR 4: bank = 16 (x & 1) + 4 s + r)
-                        if (DG == 10) x[j] = (x[j] & 0xFEFEFEFEu) | ((uint32_t)((lane >> 4) & 1) * 0x01010101u);
-                        if (GFP) {
-                            const uint32_t t02 = gf_pair(x[j], 0, tb2[j]), t13 = gf_pair(x[j], 1, tb2[j]);
-                            ad[j][0] = t02 & 0xFFFFu; ad[j][2] = t02 >> 16;
-                            ad[j][1] = t13 & 0xFFFFu; ad[j][3] = t13 >> 16;
-                        }
+                for (int j = 0; j < 4; ++j) {
+                    x[j] = zf::comp(v[j], d);
+                    if (GFP) {
+                        const uint32_t t02 = gf_pair(x[j], 0, tb2[j]), t13 = gf_pair(x[j], 1, tb2[j]);
+                        ad[j][0] = t02 & 0xFFFFu; ad[j][2] = t02 >> 16;
+                        ad[j][1] = t13 & 0xFFFFu; ad[j][3] = t13 >> 16;
                     }
+                }
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        uint32_t e[4];
+                for (int b = 0; b < 4; ++b) {
+                    uint32_t e[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            e[j] = *reinterpret_cast<const uint32_t *>(lds + (GFP ? ad[j][b] : gf_addr(x[j], b, tb[j])));
-                        // v_bitop3 (gfx950): three of the four terms in one instruction
-                        acc[d * 4 + b] = __builtin_amdgcn_bitop3_b32(e[0], e[1], e[2], 0x96) ^ e[3];
-                    }
+                    for (int j = 0; j < 4; ++j)
+                        e[j] = *reinterpret_cast<const uint32_t *>(lds + (GFP ? ad[j][b] : gf_addr(x[j], b, tb[j])));
+                    // v_bitop3 (gfx950): three of the four terms in one instruction
+                    acc[d * 4 + b] = __builtin_amdgcn_bitop3_b32(e[0], e[1], e[2], 0x96) ^ e[3];
                 }
             }
             const int wo = dofs(s) + 4 * gl;
@@ -448,13 +385,6 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
                 if (s < 7) load_step(blk, s + 1, v);
                 else if (nxt < total) load_step(nxt, 0, v);
             };
-            if (ORD == 2) next_loads();  // as soon as v is free: two compressions of cover
-            if (ORD == 3) {  // two steps ahead: v takes the next step's data, v2 loads the one after
-#pragma unroll
-                for (int t = 0; t < NV; ++t) v[t] = v2[t];
-                if (s < 6) load_step(blk, s + 2, v2);
-                else if (nxt < total) load_step(nxt, s - 6, v2);
-            }
 
             // ---- store role: whole 128-B memory lines of chunks (t, cu) ----
             // 8 B at chunk byte x (x % 8 == 0): the row's two step halves are one
@@ -471,15 +401,13 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
                     m[4 * q4] = x.x; m[4 * q4 + 1] = x.y; m[4 * q4 + 2] = x.z; m[4 * q4 + 3] = x.w;
                 }
             };
-            constexpr bool HS = DG != 2 && DG != 4 && DG != 6;  // hashing on
             uint32_t mA[16], mB[16];
-            if (MP && HS && mine) {
+            if (!FULL && mine) {
                 read_msg(0, mA);
                 read_msg(1, mB);
             }
-            constexpr bool ST = DG != 1 && DG != 4;
             u32x4 q[8];
-            if (ST && s >= 1) {  // the whole line [d + 128 (s-1), d + 128 s) of every chunk
+            if (s >= 1) {  // the whole line [d + 128 (s-1), d + 128 s) of every chunk
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
                     const uint32_t x = ldd[t] + 128u * (s - 1) + 16u * gl;
@@ -488,34 +416,12 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
                     q[t] = u32x4{lo.x, lo.y, hi.x, hi.y};
                 }
             }
-            auto one_line = [&](int t) {
-                if (DG == 8)  // diagnostic: the same stores into 8 KiB per wave (L2-resident)
-                    st16<NT>(a.out + ((uint64_t)(blockIdx.x * WPG + wave) * 8192 + t * 1024 + lane * 16), q[t]);
-                else
-                    st16<NT>(lat(t, ldd[t] + 128u * (s - 1) + 16u * gl), q[t]);
-            };
             auto line_stores = [&]() {
-                if (ST && s >= 1 && gcol && !SS) {
-                    if (DG == 7) {  // diagnostic: the piece reads without the line stores
+                if (s >= 1 && gcol) {
 #pragma unroll
-                        for (int t = 0; t < 8; ++t) h[7] ^= q[t].x ^ q[t].w;
-                    } else {
-#pragma unroll
-                        for (int t = 0; t < 8; ++t) one_line(t);
-                    }
+                    for (int t = 0; t < 8; ++t) st16(lat(t, ldd[t] + 128u * (s - 1) + 16u * gl), q[t]);
                 }
-                if (DG == 12 && s == 0 && gcol) {  // zero the level 1-3 node slots in front of each chunk
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) {
-                        const uint64_t c = (uint64_t)t * TS + ub + cu;
-                        uint32_t k = 0;
-                        for (uint32_t l = 1; l <= 3; ++l)
-                            if (c % (1ull << l) == 0 && c + (1ull << (l - 1)) < a.N) k = l;
-                        for (uint32_t i = gl; i < 8 * k; i += 8)
-                            *bao::glb(reinterpret_cast<u32x2 *>(lat_ht(t, 8 * i) - 64 * k)) = u32x2{0u, 0u};
-                    }
-                }
-                if (ST && (s == 0 || s == 7) && gcol) {
+                if ((s == 0 || s == 7) && gcol) {
 #pragma unroll
                     for (int t = 0; t < 8; ++t) {
                         const uint32_t d = ldd[t];
@@ -540,34 +446,15 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
                     }
                 }
                 // next loads, after this step's stores, in flight during the compressions
-                if (ORD <= 1) next_loads();
+                next_loads();
             };
 
             // ---- hash role: blocks 2s, 2s+1 of my chunk ----
             auto hash = [&](int hh) {
-                if (!HS) {  // keep the rows' reads alive
-                    h[hh] ^= rows[lane * RW + dofs(s) + hh];
-                } else if (mine) {
+                if (mine) {
                     const int b = 2 * s + hh;
                     const uint32_t flags = (b == 0 ? bao::F_CHUNK_START : 0u) | (b == 15 ? bao::F_CHUNK_END : 0u);
-                    if (SS && hh == 0) {
-                        uint32_t m[16];
-                        if (MP) {
-#pragma unroll
-                            for (int w = 0; w < 16; ++w) m[w] = mA[w];
-                        } else {
-                            read_msg(0, m);
-                        }
-                        const bool do_st = ST && s >= 1 && gcol && DG != 7;
-                        bao::b3_compress_cb(h, m, ci, 64, flags, [&](int r) {
-                            if (r < 4 && do_st) {
-                                __builtin_amdgcn_sched_barrier(0);
-                                one_line(2 * r);
-                                one_line(2 * r + 1);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                        });
-                    } else if (MP) {
+                    if (!FULL) {
                         bao::b3_compress(h, hh ? mB : mA, ci, 64, flags);
                     } else {
                         uint32_t m[16];
@@ -576,62 +463,27 @@ __device__ __forceinline__ void zfec_bao_fused_body(const FusedArgs &a) {
                     }
                 }
             };
-            if (ORD >= 1) {
-                if (PRIO) __builtin_amdgcn_s_setprio(0);
-                hash(0);
-                if (PRIO) __builtin_amdgcn_s_setprio(1);
-                line_stores();
-                if (PRIO) __builtin_amdgcn_s_setprio(0);
-                hash(1);
-            } else {
-                line_stores();
-                hash(0);
-                hash(1);
-            }
+            hash(0);
+            line_stores();
+            hash(1);
             bao::wave_sync();
         }
         if (FULL) {
             tree.step(h, ob + hco - 64, obj * 8 * a.cvs + ci, true);
-        } else if (RUNS) {
-            // row t's aligned group that this block completes: columns [ub - d, ub - d + 8),
-            // element j held by lane 8t + ((j - d) & 7) of this block (j >= d) or of the
-            // previous one (j < d), d = the row's offset from the 8-chunk grid
-            const int t = lane >> 3, j = lane & 7;
-            const uint32_t d = (uint32_t)(((uint64_t)t * a.cols) & 7);
-            const uint64_t gc0 = (uint64_t)t * a.cols + ub - d;  // its first chunk
-            const bool ok = ub >= d && group_in_wave(gc0 / 8, a.cols, a.bpo, RT);
-            const int src = (lane & ~7) | ((j - (int)d) & 7);
-            uint32_t g[8];
-#pragma unroll
-            for (int w = 0; w < 8; ++w) {
-                const uint32_t x = (uint32_t)__shfl((int)h[w], src), y = (uint32_t)__shfl((int)hp[w], src);
-                g[w] = j >= (int)d ? x : y;
-                hp[w] = h[w];
-            }
-            const uint64_t ec = gc0 + j;  // my element's chunk
-            tree.step(g, ob + (ok ? a.coff[ec] : 64) - 64, obj * 8 * a.cvs + ec, ok);
-            // my own chunk's level-0 CV when its group is left to the level-1-3 pass
-            if (mine && !group_in_wave(ci / 8, a.cols, a.bpo, RT)) {
-                auto *cvp = bao::glb(reinterpret_cast<u32x4 *>(a.cv + (obj * a.N + ci) * 32));
-                cvp[0] = u32x4{h[0], h[1], h[2], h[3]};
-                cvp[1] = u32x4{h[4], h[5], h[6], h[7]};
-            }
-        } else if (mine && DG != 13) {
-            const uint64_t cvi = DG == 14 ? obj * 8 * (8 * a.bpo) + (uint64_t)(lane >> 3) * (8 * a.bpo) + hu
-                                          : obj * a.N + ci;
-            auto *cvp = bao::glb(reinterpret_cast<u32x4 *>(a.cv + cvi * 32));
+        } else if (mine) {
+            auto *cvp = bao::glb(reinterpret_cast<u32x4 *>(a.cv + (obj * a.N + ci) * 32));
             cvp[0] = u32x4{h[0], h[1], h[2], h[3]};
             cvp[1] = u32x4{h[4], h[5], h[6], h[7]};
         }
     }
-    if (FULL || RUNS) {  // drain: level 2 of the last block, level 3 of the last two
+    if (FULL) {  // drain: level 2 of the last block, level 3 of the last two
         uint32_t z[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
         tree.step(z, nullptr, 0, false);
         tree.step(z, nullptr, 0, false);
     }
-    if (DQ && lane == 0) {  // the last wave out leaves the queue zero for the next launch
+    if (lane == 0) {  // the last wave out leaves the queue zero for the next launch
         const uint32_t done = atomicAdd(a.queue + 32, 1u);
-        if (done + 1 == gridDim.x * (uint32_t)WPG) {
+        if (done + 1 == waves) {
             a.queue[0] = 0u;
             a.queue[32] = 0u;
         }
@@ -773,8 +625,9 @@ __global__ __launch_bounds__(256) void bao_levels123_kernel(const uint8_t *cv0, 
 // at 64 places 8 KiB apart.  QS: nodes per lane staged at once (4: a whole
 // level, 16 KiB of LDS per wave; 1: node by node, 4 KiB, so LDS no longer
 // caps the waves per CU below what the registers allow).
-// rt > 0: only the groups K13's run mode left (group_in_wave false; cols,
-// bpo: the zfec shards' chunk-columns and K13's blocks per object).
+// rt > 0: only the groups a run-mode K13 would leave (group_in_wave false;
+// cols, bpo: the zfec shards' chunk-columns and K13's blocks per object).
+// Every launch passes 0: K13 completes no group of the general path.
 // L > 0: levels L+1..L+3 from the N level-L CVs per object in cv0 (the same
 // groups of 8 one level-L stride up: a level-(L+l) node whose leftmost chunk
 // is c sits 64 (L + l) bytes before chunk c, its left spine being complete),

@@ -49,30 +49,27 @@ namespace fused {
 // The product's K13 configurations (fused_device.hpp documents the template
 // arguments): encode() at Zfec|Bao with levels 1-3 in the wave (FULL) or from
 // the level-0 CVs (general: 8 does not divide the shard's chunk count, or
-// zfec padding; both message words of a step read at once, MP 1: -1.5 %
+// zfec padding; both message words of a step read at once there: -1.5 %
 // kernel time, tools/fused_tune, profiles/r6f/r6h/r6i; the FULL path measured
 // no gain from it), and bao of the content (KIND 1).  _a64: 64-bit addresses
 // for shards of 256 MiB and more.
 __global__ __launch_bounds__(fused::FTPB) void zfec_bao_fused_kernel_full(fused::FusedArgs a) {
-    fused::zfec_bao_fused_body<true, true, 1, 0, 0, true, 0, 0, K13_O32, K13_GFP>(a);
+    fused::zfec_bao_fused_body<true, 0, K13_O32, K13_GFP>(a);
 }
-// (The general path's run mode, fused_device.hpp RT, is a tuner variant: the
-// kernel 13 % slower than this one at the level-15 shard length, the pipeline
-// line 962 against 1009 GiB/s, profiles/r10e_session.)
 __global__ __launch_bounds__(fused::FTPB) void zfec_bao_fused_kernel_general(fused::FusedArgs a) {
-    fused::zfec_bao_fused_body<true, false, 1, 0, 0, true, 1, 0, K13_O32, K13_GFP>(a);
+    fused::zfec_bao_fused_body<false, 0, K13_O32, K13_GFP>(a);
 }
 __global__ __launch_bounds__(fused::FTPB) void zfec_bao_fused_kernel_full_a64(fused::FusedArgs a) {
-    fused::zfec_bao_fused_body<true, true, 1, 0, 0, true, 0, 0, false, K13_GFP>(a);
+    fused::zfec_bao_fused_body<true, 0, false, K13_GFP>(a);
 }
 __global__ __launch_bounds__(fused::FTPB) void zfec_bao_fused_kernel_general_a64(fused::FusedArgs a) {
-    fused::zfec_bao_fused_body<true, false, 1, 0, 0, true, 1, 0, false, K13_GFP>(a);
+    fused::zfec_bao_fused_body<false, 0, false, K13_GFP>(a);
 }
 __global__ __launch_bounds__(fused::FTPB) void bao_content_fused_kernel(fused::FusedArgs a) {
-    fused::zfec_bao_fused_body<true, true, 1, 0, 1, true, 0, 0, K13_O32, 0, fused::FW, K13_NTL>(a);
+    fused::zfec_bao_fused_body<true, 1, K13_O32, 0, K13_NTL>(a);
 }
 __global__ __launch_bounds__(fused::FTPB) void bao_content_fused_kernel_a64(fused::FusedArgs a) {
-    fused::zfec_bao_fused_body<true, true, 1, 0, 1>(a);
+    fused::zfec_bao_fused_body<true, 1>(a);
 }
 
 }  // namespace fused
@@ -92,7 +89,6 @@ hipError_t launch_parts(const fused::FusedArgs &a, uint64_t cv_nodes, void (*ker
         p.in = a.in + o0 * a.in_stride;
         p.out = a.out + o0 * a.out_stride;
         p.cv = a.cv + o0 * cv_nodes * 32;
-        if (a.cv3) p.cv3 = a.cv3 + o0 * a.cvs * 32;
         const uint64_t blocks = p.count * p.bpo;
         uint64_t grid = (blocks + FW - 1) / FW;
         const uint64_t cap = (uint64_t)num_cus();  // one workgroup (8 waves) per CU fits the LDS

@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <type_traits>
 
 #include "chip_internal.hpp"
 #include "layout_store.hpp"
@@ -26,52 +25,46 @@ struct ApplyArgs {
     uint8_t *out;
     uint64_t in_stride, out_stride, valid, C;
     uint64_t tiles_per_obj, total_tiles, count;
-    uint64_t chunk;                    // MAP 3: tiles per XCD-grouped run (>= 1)
+    uint64_t chunk;                    // tiles per run of the run queue (>= 1)
     const void *table;                 // [K][256] entries of NG dwords
     const uint64_t *bao_off;           // BL: stream offset of each 1 KiB chunk of the shard-major output
     uint64_t bao_n;                    // BL: number of chunks (bao_off entries)
     uint64_t in_off[ZF_MAXK];
     uint64_t copy_off[ZF_MAXK];
     uint64_t par_off[ZF_MAXP];
-    uint32_t *queue;                   // MAP 6/7: run counters (QueueIter), zero at launch, left zero
-    uint32_t xcd_mask;                 // MAP 6/7: XCDs whose workgroups take runs (0 = all)
-    uint64_t *trace;                   // TR: per-workgroup {start, end, xcc, tiles} (tools only)
+    uint32_t *queue;                   // run counters (QueueIter), zero at launch, left zero
+    uint32_t xcd_mask;                 // XCDs whose workgroups take runs (0 = all)
 };
 
 // Hardware XCC (XCD) id of the executing workgroup (gfx940+ HW_REG_XCC_ID).
 __device__ __forceinline__ uint32_t xcc_id() { return __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u; }
 
-// Dynamic run queue (MAP 6 and 7).  The tile space is cut into runs of CH
-// consecutive tiles, the runs into 8 shares, one per XCD.  A workgroup takes
-// the next run of its own XCD's share (one device-scope atomic per run, by
-// thread 0, broadcast through LDS) and, once that share is exhausted, runs
-// of the following XCDs' shares: the XCDs that stream faster finish the
-// slower ones' work instead of idling at the end of the launch.
-//   MAP 6: share x = the x-th contiguous eighth of the runs;
-//   MAP 7: MAP 3's interleave (the XCD's G/8 workgroups' runs of each
-//          round of G runs), so all XCDs sweep one window of the batch.
+// Dynamic run queue: the tile schedule.  The tile space is cut into runs of CH
+// consecutive tiles, the runs into 8 shares, one per XCD: share x = the x-th
+// contiguous eighth of the runs.  A workgroup takes the next run of its own
+// XCD's share (one device-scope atomic per run, by thread 0, broadcast
+// through LDS) and, once that share is exhausted, runs of the following XCDs'
+// shares: the XCDs that stream faster finish the slower ones' work instead of
+// idling at the end of the launch.
 // q[32 x] = run counter of share x, q[256] = workgroups done; the last
 // workgroup to finish zeroes them, so every launch finds them zero.
-template <int MAP>
+// (The static tile orders and the interleaved shares this replaced are in
+// profiles/NOT_KEPT.md.)
 struct QueueIter {
     uint32_t *q, *slot;
-    uint64_t R, T, CH, g, run = 0, t_in = 0, rl = 0;
-    uint32_t xcc, v = 0, k = 0;
+    uint64_t R, T, CH, run = 0, t_in = 0, rl = 0;
+    uint32_t G, xcc, v = 0, k = 0;  // G: workgroups of the grid
     __device__ QueueIter(uint64_t total, uint64_t ch, uint32_t *queue, uint32_t *lds_slot, uint32_t mask)
         : q(queue), slot(lds_slot), T(total), CH(ch < 1 ? 1 : ch) {
         R = (T + CH - 1) / CH;
-        g = gridDim.x / 8 ? gridDim.x / 8 : 1;
+        G = gridDim.x;
         xcc = xcc_id();
         if (mask && !((mask >> xcc) & 1u)) v = 8;  // this XCD sits out: the others take its share
     }
     // run index of the i-th run of share x, or ~0 past its end
     __device__ uint64_t share_run(uint32_t x, uint64_t i) const {
-        if (MAP == 6) {
-            const uint64_t lo = x * R / 8, hi = (x + 1) * R / 8;
-            return lo + i < hi ? lo + i : ~0ull;
-        }
-        const uint64_t r = (i / g) * (8 * g) + x * g + (i % g);
-        return r < R ? r : ~0ull;
+        const uint64_t lo = x * R / 8, hi = (x + 1) * R / 8;
+        return lo + i < hi ? lo + i : ~0ull;
     }
     __device__ bool grab() {
         uint32_t *s = slot + (k++ & 1);  // double-buffered: one barrier per grab
@@ -104,7 +97,7 @@ struct QueueIter {
         __syncthreads();
         if (threadIdx.x == 0) {
             __threadfence();
-            if (atomicAdd(q + 256, 1u) == gridDim.x - 1) {
+            if (atomicAdd(q + 256, 1u) == G - 1) {
                 for (int x = 0; x < 8; ++x) atomicExch(q + 32 * x, 0u);
                 atomicExch(q + 256, 0u);
             }
@@ -182,91 +175,16 @@ __device__ __forceinline__ uint32_t gf_double4(uint32_t c) {
     return ((c & 0x7F7F7F7Fu) << 1) ^ (((c >> 7) & 0x01010101u) * 0x1Du);
 }
 
-// Tile schedule (MAP), per workgroup b of G:
-//   0  grid-stride: tile = b, b + G, b + 2G, ...
-//   1  XCD-grouped grid-stride: the G/8 workgroups that share an XCD
-//      (b % 8, observed round-robin dispatch; speed only, never correctness)
-//      take G/8 consecutive tiles each round
-//   2  one contiguous range per workgroup
-//   3  XCD-grouped chunks: runs of CH consecutive tiles dealt as in 1, each
-//      run walked in order by one workgroup (long sequential streams per
-//      shard; tools/write_probe: HBM writes 5.0 -> 5.9 TB/s)
-//   5  as 3, each workgroup starting its runs at its own rotated tile (a
-//      per-workgroup offset mod CH, wrapping inside the run).  Runs begin at
-//      multiples of CH tiles in every object and shard, so under 3 all
-//      workgroups advance in lockstep at the same offset inside their runs
-//      and every stream in flight shares the same low address bits.
-// Falls back to 0 when G is not a multiple of 8.
-template <int MAP>
-struct TileIter {
-    uint64_t T, c, t_in, end, stride, base, CH;
-    uint64_t rot = 0, rl = 0, rotr = 0;  // MAP 5: rotation, current run length, rotation mod rl
-    int mode;
-    __device__ void start_run() {
-        rl = c * CH >= T ? 0 : (T - c * CH < CH ? T - c * CH : CH);
-        rotr = rl == CH ? rot : (rl ? rot % rl : 0);
-    }
-    __device__ TileIter(uint64_t total, uint64_t ch) : T(total), t_in(0), CH(ch < 1 ? 1 : ch) {
-        const uint64_t G = gridDim.x, b = blockIdx.x;
-        mode = ((MAP == 1 || MAP == 3 || MAP == 5) && (G & 7)) ? 0 : MAP;
-        if (mode == 2) {
-            const uint64_t chunk = (T + G - 1) / G;
-            c = b * chunk;
-            end = c + chunk < T ? c + chunk : T;
-            stride = 1;
-            base = 0;
-        } else if (mode == 1 || mode == 3 || mode == 5) {
-            base = (b % 8) * (G / 8) + b / 8;
-            c = base;
-            stride = G;
-            end = T;
-            if (mode == 5) {
-                rot = (b * 37 + (b >> 3)) % CH;
-                start_run();
-            }
-        } else {
-            c = b;
-            stride = G;
-            end = T;
-            base = 0;
-        }
-    }
-    __device__ bool next(uint64_t &t) {
-        if (mode == 5) {
-            if (t_in == rl) {
-                c += stride;
-                t_in = 0;
-                start_run();
-            }
-            if (rl == 0) return false;
-            uint64_t i = t_in + rotr;
-            if (i >= rl) i -= rl;
-            t = c * CH + i;
-            ++t_in;
-            return true;
-        }
-        if (mode == 3) {
-            if (t_in == CH) { c += stride; t_in = 0; }
-            t = c * CH + t_in;
-            ++t_in;
-            return t < T;
-        }
-        t = c;
-        c += stride;
-        return t < end;
-    }
-};
-
-// The kernel body.  RO: replica-count override, WPE: waves/EU hint, SB:
-// scheduling fence every SB shards (bounds the table lookups in flight; 0 =
-// none), PF: load the next super-tile's shards before computing the current
-// one, NTL: nontemporal input loads, TR: per-workgroup trace — tools/zfec_tune.
+// The kernel body.  K input shards, NG dword groups of computed rows, U column
+// tiles per super-tile, NT: nontemporal stores, SB: scheduling fence every SB
+// shards (bounds the table lookups in flight; 0 = none), PF: load the next
+// super-tile's shards before computing the current one, NTL: nontemporal
+// input loads.  Tiles come from the run queue (QueueIter).
 // The product's kernels are zfec_kernels.hip's zfec_apply_kernel<K, NG> (one
 // configuration per shape, ApplyCfg); the tuner's, tools/zfec_variants.hpp's.
-template <int K, int NG, int U, int MAP, bool NT, int RO = 0, int WPE = 1, int SB = 0, bool PF = false,
-          bool NTL = false, bool TR = false>
+template <int K, int NG, int U, bool NT, int SB = 0, bool PF = false, bool NTL = false>
 __device__ __forceinline__ void gf_apply_body(const ApplyArgs &a) {
-    constexpr int R = RO ? RO : replicas_for(K);
+    constexpr int R = replicas_for(K);
     using E = typename Entry<NG>::T;
     constexpr int W = 4 * NG;            // bytes per table entry
     constexpr int ROWB = K * R * W;      // bytes per table row (one byte value x)
@@ -299,14 +217,8 @@ __device__ __forceinline__ void gf_apply_body(const ApplyArgs &a) {
 
     // super-tiles of U adjacent column tiles of one object
     const uint64_t spo = (a.tiles_per_obj + U - 1) / U;
-    uint64_t t_start = 0, n_tiles = 0;
-    if constexpr (TR) t_start = wall_clock64();
     __shared__ uint32_t q_slot[2];
-    using Iter = typename std::conditional<(MAP >= 6), QueueIter<MAP>, TileIter<MAP>>::type;
-    Iter iter = [&] {
-        if constexpr (MAP >= 6) return Iter(spo * a.count, a.chunk, a.queue, q_slot, a.xcd_mask);
-        else return Iter(spo * a.count, a.chunk);
-    }();
+    QueueIter iter(spo * a.count, a.chunk, a.queue, q_slot, a.xcd_mask);
     auto load_tile = [&](uint64_t t, u32x4 (&v)[U][K]) {
         const uint64_t obj = t / spo;
         const uint64_t col0 = (t - obj * spo) * (uint64_t)(U * TILE) + threadIdx.x * VEC;
@@ -403,18 +315,8 @@ __device__ __forceinline__ void gf_apply_body(const ApplyArgs &a) {
         }
         st = st_next;
         have = have_next;
-        if constexpr (TR) ++n_tiles;
     }
-    if constexpr (MAP >= 6) iter.finish();
-    if constexpr (TR) {
-        if (threadIdx.x == 0) {
-            uint64_t *tr = a.trace + 4 * blockIdx.x;
-            tr[0] = t_start;
-            tr[1] = wall_clock64();
-            tr[2] = xcc_id();
-            tr[3] = n_tiles;
-        }
-    }
+    iter.finish();
 }
 
 // BL (bao layout, encode() with Zfec|Bao): zfec 4-of-8 encode whose 8 output

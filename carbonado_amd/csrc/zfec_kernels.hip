@@ -103,7 +103,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(2))) void h
     }
     const uint64_t spo = (a.tiles_per_obj + U - 1) / U;
     __shared__ uint32_t q_slot[2];
-    QueueIter<6> iter(spo * a.count, a.chunk, a.queue, q_slot, a.xcd_mask);
+    QueueIter iter(spo * a.count, a.chunk, a.queue, q_slot, a.xcd_mask);
     auto load_tile = [&](uint64_t t, u32x4 (&v)[U][K]) {
         const uint64_t obj = t / spo;
         const uint64_t col0 = (t - obj * spo) * (uint64_t)(U * TILE) + threadIdx.x * VEC;
@@ -156,15 +156,14 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(2))) void h
 typedef void (*KernelFn)(ApplyArgs);
 
 // Schedule.  Every shape walks its column tiles through the
-// dynamic per-XCD run queue (MAP 6, QueueIter): runs of ZF_CHUNK tiles (256
+// dynamic per-XCD run queue (QueueIter): runs of ZF_CHUNK tiles (256
 // KiB per shard) dealt from 8 contiguous shares of the batch, one per XCD,
 // and once an XCD's share is done it takes runs of the others'.  The XCDs
 // do not stream at the same rate (odd XCDs ~20 % slower on every box
-// measured, tools/zfec_timeline), so the static XCD-grouped order this
-// replaces (MAP 3) ended with half the chip idle for the last ~1 ms of a
-// 10 ms launch; the queue ends every XCD within ~0.1 ms (+2.5-3 % on the
-// headline, and it needs no per-box schedule choice).
-constexpr int ZF_MAP = 6;
+// measured with per-workgroup traces, profiles/NOT_KEPT.md), so the static
+// XCD-grouped order this replaces ended with half the chip idle for the last
+// ~1 ms of a 10 ms launch; the queue ends every XCD within ~0.1 ms (+2.5-3 %
+// on the headline, and it needs no per-box schedule choice).
 constexpr bool ZF_NT = true;
 constexpr uint64_t ZF_CHUNK = 64;   // tiles per run (U = 1 tiles; U = 2 super-tiles run ZF_CHUNK / 2)
 constexpr uint64_t ZF_BL_RUN = 32;  // bao-layout kernel: consecutive 1 KiB units per wave run
@@ -205,7 +204,7 @@ template <int K, int NG>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(ApplyCfg<K, NG>::WPE))) void zfec_apply_kernel(
     ApplyArgs a) {
     using C = ApplyCfg<K, NG>;
-    gf_apply_body<K, NG, C::U, ZF_MAP, C::NT, 0, C::WPE, C::SB, C::PF, C::NTL>(a);
+    gf_apply_body<K, NG, C::U, C::NT, C::SB, C::PF, C::NTL>(a);
 }
 
 template <int K, int NG>

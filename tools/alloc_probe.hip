@@ -59,11 +59,11 @@ struct Variant {
     int bpc, chunk;
 };
 
-template <int U, int MAP, int CH, int WPE>
+template <int U, int CH, int WPE>
 Variant V(int bpc) {
     char buf[64];
-    snprintf(buf, sizeof buf, "U%d MAP%d CH%-3d bpc%d", U, MAP, CH, bpc);
-    return Variant{buf, gf_apply_kernel<4, 1, U, MAP, true, 0, WPE, 0, true>, bpc, CH};
+    snprintf(buf, sizeof buf, "U%d CH%-3d bpc%d", U, CH, bpc);
+    return Variant{buf, gf_apply_kernel<4, 1, U, true, WPE, 0, true>, bpc, CH};
 }
 
 struct Buf {
@@ -174,7 +174,7 @@ int main(int argc, char **argv) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    std::vector<Variant> vs = {V<2, 3, 32, 2>(2), V<2, 6, 32, 2>(2), V<2, 7, 32, 2>(2), V<1, 6, 16, 1>(4)};
+    std::vector<Variant> vs = {V<2, 32, 2>(2), V<1, 16, 1>(4)};
     struct Alloc { std::string name; int kind; uint64_t chunk; bool shuffle; bool reuse = false; };
     const uint64_t MiB = 1ull << 20;
     std::vector<Alloc> allocs = {{"balanced", 3, 0, false},

@@ -10,14 +10,14 @@
 namespace chip {
 namespace bao {
 
-template <int MODE, int CPL, bool NTS, int SP = 0, int SU = 1, int SE = 0, int XG = 0, bool DQ = false>
+template <int MODE, int CPL, bool NTS, int SP = 0, int SU = 1, bool DQ = false>
 __global__ __launch_bounds__(K3_TPB) void bao_chunk_kernel(ChunkArgs a) {
-    bao_chunk_body<MODE, CPL, NTS, SP, SU, SE, XG, DQ>(a);
+    bao_chunk_body<MODE, CPL, NTS, SP, SU, DQ>(a);
 }
 
-template <int MODE, int CPL, bool NTS, int SP, int SU, int SE, int XG, bool DQ>
+template <int MODE, int CPL, bool NTS, int SP, int SU, bool DQ>
 struct ChunkKernel {
-    static constexpr void (*fn)(ChunkArgs) = bao_chunk_kernel<MODE, CPL, NTS, SP, SU, SE, XG, DQ>;
+    static constexpr void (*fn)(ChunkArgs) = bao_chunk_kernel<MODE, CPL, NTS, SP, SU, DQ>;
 };
 
 }  // namespace bao

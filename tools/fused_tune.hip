@@ -1,5 +1,5 @@
-// fused_tune.hip — K13 (carbonado_amd/csrc/fused_device.hpp) variants and
-// diagnostics on 256 x 16 MiB objects, interleaved in one process.  Times
+// fused_tune.hip — K13 (carbonado_amd/csrc/fused_device.hpp) variants
+// on 256 x 16 MiB objects, interleaved in one process.  Times
 // the fused kernel alone (the parent levels are not run).  Calibration tool.
 //   fused_tune [objects=256] [rounds=3] [variant-name filter]
 #include <hip/hip_runtime.h>
@@ -39,8 +39,8 @@ __global__ void fill_kernel(uint64_t *p, size_t n, uint64_t seed) {
     }
 }
 
-// order-sensitive checksum of a buffer (the tuner compares every non-DG
-// variant's stream and CVs with the first variant's)
+// order-sensitive checksum of a buffer (the tuner compares every variant's
+// stream and CVs with the first variant's of its kind and path)
 __global__ void checksum_kernel(const uint64_t *p, size_t n, unsigned long long *out) {
     unsigned long long acc = 0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
@@ -110,57 +110,26 @@ int main(int argc, char **argv) {
         a.cvs = a.N / 8;  // level-3 CVs per object (FULL)
     }
     const char *which = argc > 3 ? argv[3] : "all";
+    // <FULL, KIND, O32, GFP, NTL>; the first row of a kind and path is the reference of its outputs
     std::vector<Variant> all = {
-        {"K0 FULL (product)", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 1>, 0},
-        {"K0 FULL O32 GFP0", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 0>, 0},
-        {"K0 FULL O32=0 GFP0 (r6 product)", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0>, 0},
-        {"K0 FULL K13S spec", fused::zfec_bao_spec_kernel<true>, 0, true},
-        {"K0 FULL product PRIO1 (GF/stores at raised priority)", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 1, 8, false, 1>, 0},
-        {"K1 product PRIO1 (loads/stores at raised priority)", fused::zfec_bao_fused_kernel<true, true, 1, 0, 1, true, 0, 0, true, 0, 8, true, 1>, 1},
-        {"K1 product NTL (as the library)", fused::zfec_bao_fused_kernel<true, true, 1, 0, 1, true, 0, 0, true, 0, 8, true>, 1},
-        {"K0 FULL product NTL (nontemporal loads)", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 1, 8, true>, 0},
-        {"K0 FULL product WPG4 (1 wave/SIMD)", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 1, 4>, 0},
-        {"K0 FULL K13S spec NPB1", fused::zfec_bao_spec_kernel<true, 1>, 0, true},
-        {"K0 FULL MP1", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 1>, 0},
-        {"K0 FULL ORD2 MP1", fused::zfec_bao_fused_kernel<true, true, 2, 0, 0, true, 1>, 0},
-        {"K1 MP1", fused::zfec_bao_fused_kernel<true, true, 1, 0, 1, true, 1>, 1},
-        {"K0 general MP1", fused::zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 1>, 0},
-        {"K0 general ORD2", fused::zfec_bao_fused_kernel<true, false, 2, 0, 0, true, 0>, 0},
-        {"K0 general ORD2 MP1", fused::zfec_bao_fused_kernel<true, false, 2, 0, 0, true, 1>, 0},
-        {"K0 FULL ORD2 NT0", fused::zfec_bao_fused_kernel<false, true, 2, 0, 0>, 0},
-        {"K0 general ORD2 NT0", fused::zfec_bao_fused_kernel<false, false, 2, 0, 0>, 0},
-        {"K0 FULL ORD0", fused::zfec_bao_fused_kernel<true, true, 0, 0, 0>, 0},
-        {"K0 FULL ORD2", fused::zfec_bao_fused_kernel<true, true, 2, 0, 0>, 0},
-        {"K0 FULL ORD3", fused::zfec_bao_fused_kernel<true, true, 3, 0, 0>, 0},
-        {"K1 ORD2", fused::zfec_bao_fused_kernel<true, true, 2, 0, 1>, 1},
-        {"K1 ORD3", fused::zfec_bao_fused_kernel<true, true, 3, 0, 1>, 1},
-        {"K0 general", fused::zfec_bao_fused_kernel<true, false, 1, 0, 0>, 0},
-        {"K1 (product)", fused::zfec_bao_fused_kernel<true, true, 1, 0, 1>, 1},
-        {"K0 DG1 no line stores/reads", fused::zfec_bao_fused_kernel<true, true, 1, 1, 0>, 0},
-        {"K0 DG7 piece reads, no stores", fused::zfec_bao_fused_kernel<true, true, 1, 7, 0>, 0},
-        {"K0 DG2 no hash", fused::zfec_bao_fused_kernel<true, true, 1, 2, 0>, 0},
-        {"K0 DG8 line stores to L2", fused::zfec_bao_fused_kernel<true, true, 1, 8, 0>, 0},
-        {"K0 FULL SS1", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 1>, 0},
-        {"K0 FULL SS1 ORD2", fused::zfec_bao_fused_kernel<true, true, 2, 0, 0, true, 0, 1>, 0},
-        {"K0 general SS1 MP1", fused::zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 1, 1>, 0},
-        {"K1 SS1", fused::zfec_bao_fused_kernel<true, true, 1, 0, 1, true, 0, 1>, 1},
-        {"K0 DG8 ORD2 line stores to L2", fused::zfec_bao_fused_kernel<true, true, 2, 8, 0>, 0},
-        {"K0 DG5 aligned lines", fused::zfec_bao_fused_kernel<true, true, 1, 5, 0>, 0},
-        {"K1 DG5 aligned lines", fused::zfec_bao_fused_kernel<true, true, 1, 5, 1>, 1},
-        {"K1 DG1 no line stores/reads", fused::zfec_bao_fused_kernel<true, true, 1, 1, 1>, 1},
-        {"K1 DG7 piece reads, no stores", fused::zfec_bao_fused_kernel<true, true, 1, 7, 1>, 1},
-        {"K1 DG2 no hash", fused::zfec_bao_fused_kernel<true, true, 1, 2, 1>, 1},
-        {"K0 FULL K13S spec (again)", fused::zfec_bao_spec_kernel<true>, 0, true},
-        {"K0 FULL (product, again)", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 1>, 0},
-        // round 4: occupancy and LDS-conflict diagnostics (wrong output)
-        {"K0 DG10 GF lookups conflict-free", fused::zfec_bao_fused_kernel<true, true, 1, 10, 0, true, 0, 0, true, 1>, 0},
-        {"K0 DG3 no GF (product params)", fused::zfec_bao_fused_kernel<true, true, 1, 3, 0, true, 0, 0, true, 1>, 0},
-        {"K0 DG1 no line stores/reads (product params)", fused::zfec_bao_fused_kernel<true, true, 1, 1, 0, true, 0, 0, true, 1>, 0},
-        {"K0 DG7 piece reads, no stores (product params)", fused::zfec_bao_fused_kernel<true, true, 1, 7, 0, true, 0, 0, true, 1>, 0},
-        {"K0 DG-occ WPG12 3 waves/SIMD rows aliased", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 1, 12>, 0},
-        {"K0 general product", fused::zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 1, 0, true, 1>, 0},
-        {"K0 general DG-occ WPG12 3 waves/SIMD rows aliased", fused::zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 1, 0, true, 1, 12>, 0},
-        {"K0 FULL (product, third)", fused::zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 1>, 0}};
+        {"K0 FULL (product)", fused::zfec_bao_fused_kernel<true, 0, true, 1>, 0},
+        {"K0 FULL O32 GFP0", fused::zfec_bao_fused_kernel<true, 0, true, 0>, 0},
+        {"K0 FULL O32=0 (product, shards of 256 MiB and more)", fused::zfec_bao_fused_kernel<true, 0, false, 1>, 0},
+        {"K0 FULL O32=0 GFP0 (r6 product)", fused::zfec_bao_fused_kernel<true, 0>, 0},
+        {"K0 FULL K13S spec", fused::zfec_bao_spec_kernel<>, 0, true},
+        {"K1 product NTL (as the library)", fused::zfec_bao_fused_kernel<true, 1, true, 0, true>, 1},
+        {"K0 FULL product NTL (nontemporal loads)", fused::zfec_bao_fused_kernel<true, 0, true, 1, true>, 0},
+        {"K0 FULL K13S spec NPB1", fused::zfec_bao_spec_kernel<1>, 0, true},
+        {"K0 general product", fused::zfec_bao_fused_kernel<false, 0, true, 1>, 0},
+        {"K0 general O32=0 (product, shards of 256 MiB and more)", fused::zfec_bao_fused_kernel<false, 0, false, 1>, 0},
+        {"K0 general O32=0 GFP0", fused::zfec_bao_fused_kernel<false, 0>, 0},
+        {"K0 general product NTL", fused::zfec_bao_fused_kernel<false, 0, true, 1, true>, 0},
+        {"K1 O32=0 (product, objects of 256 MiB and more)", fused::zfec_bao_fused_kernel<true, 1>, 1},
+        {"K1 O32 plain loads", fused::zfec_bao_fused_kernel<true, 1, true>, 1},
+        {"K0 FULL K13S spec (again)", fused::zfec_bao_spec_kernel<>, 0, true},
+        {"K0 FULL (product, again)", fused::zfec_bao_fused_kernel<true, 0, true, 1>, 0},
+        {"K0 general product (again)", fused::zfec_bao_fused_kernel<false, 0, true, 1>, 0},
+        {"K0 FULL (product, third)", fused::zfec_bao_fused_kernel<true, 0, true, 1>, 0}};
     std::vector<Variant> vs;
     for (auto &v : all)
         if (!strcmp(which, "all") || strstr(v.name.c_str(), which)) vs.push_back(v);
@@ -178,8 +147,7 @@ int main(int argc, char **argv) {
             const uint64_t blocks = count * a.bpo;
             const unsigned grid = (unsigned)std::min<uint64_t>(256, (blocks + fused::FW - 1) / fused::FW);
             const unsigned tpb = vs[v].spec ? (vs[v].name.find("NPB1") != std::string::npos ? fused::stpb<1>() : fused::STPB)
-                                 : vs[v].name.find("WPG4") != std::string::npos ? 256u
-                                 : vs[v].name.find("WPG12") != std::string::npos ? 768u : fused::FTPB;
+                                            : fused::FTPB;
             const size_t ldsb = vs[v].spec ? fused::S_LDS_BYTES : fused::LDS_BYTES;
             hipLaunchKernelGGL(vs[v].fn, dim3(grid), dim3(tpb), ldsb, 0, a);
             CK(hipEventRecord(e0));
@@ -205,7 +173,7 @@ int main(int argc, char **argv) {
             fused::bao_levels123_kernel<1>, fused::bao_levels123_kernel<2>, fused::bao_levels123_kernel<0>, nullptr,
             fused::bao_levels123_seg_kernel};
         void (*kq[8])(const uint8_t *, uint64_t, uint64_t, const uint64_t *, uint8_t *, uint64_t, uint8_t *, uint64_t,
-                      uint64_t, uint64_t, uint64_t) = {nullptr, nullptr, nullptr, fused::bao_levels123_lds_kernel<4>,
+                      uint64_t, uint64_t, uint64_t, uint32_t) = {nullptr, nullptr, nullptr, fused::bao_levels123_lds_kernel<4>,
                                                        nullptr, fused::bao_levels123_lds_kernel<1>,
                                                        fused::bao_levels123_lds_kernel<2>,
                                                        fused::bao_levels123_lds_kernel<4>};
@@ -224,7 +192,7 @@ int main(int argc, char **argv) {
                 if (kq[k])
                     hipLaunchKernelGGL(kq[k], dim3((unsigned)((work + tpb - 1) / tpb)), dim3(tpb), 0, 0, cv, N, count,
                                        dcoff[0], out + (k == 7 ? 56 : 0), bstride, cv3, n3, (uint64_t)0,
-                                       (uint64_t)0, (uint64_t)0);
+                                       (uint64_t)0, (uint64_t)0, (uint32_t)0);
                 else
                     hipLaunchKernelGGL(kv[k], dim3((unsigned)((work + tpb - 1) / tpb)), dim3(tpb), 0, 0, cv, N, count,
                                        dcoff[0], out, bstride, cv3, n3);
@@ -251,13 +219,10 @@ int main(int argc, char **argv) {
         const double m = t[t.size() / 2];
         // 672 lane-ops per compression, 16 per chunk
         const double ops = (double)count * A[vs[v].kind].N * 16 * 672;
-        const bool diag = vs[v].name.find("DG") != std::string::npos;
         size_t ref = 0;
         auto general = [&](size_t i) { return vs[i].name.find("general") != std::string::npos; };
-        while (ref < vs.size() && (vs[ref].kind != vs[v].kind || general(ref) != general(v) ||
-                                   vs[ref].name.find("DG") != std::string::npos))
-            ++ref;
-        const char *chk = diag ? "(diagnostic)" : (ref < vs.size() && sums[ref] == sums[v] ? "output = first" : "OUTPUT DIFFERS");
+        while (ref < vs.size() && (vs[ref].kind != vs[v].kind || general(ref) != general(v))) ++ref;
+        const char *chk = ref < vs.size() && sums[ref] == sums[v] ? "output = first" : "OUTPUT DIFFERS";
         printf("%-16s ", chk);
         printf("%-26s median %7.3f ms  -> %6.1f GiB/s input, %.3f of VALU (chunk compressions only)\n",
                vs[v].name.c_str(), m, count * n / (m * 1e-3) / 1073741824.0, ops / (m * 1e-3) / 39.3e12);

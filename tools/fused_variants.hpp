@@ -16,10 +16,9 @@ namespace fused {
 // (fused_device.hpp zfec_bao_fused_body documents the arguments), each its
 // own kernel.  The library instantiates only the configurations it ships
 // (fused_kernels.hip: zfec_bao_fused_kernel_full / _general, ...).
-template <bool NT, bool FULL, int ORD = 1, int DG = 0, int KIND = 0, bool DQ = true, int MP = 0, int SS = 0,
-          bool O32 = false, int GFP = 0, int WPG = FW, bool NTL = false, int PRIO = 0, int RT = 0>
-__global__ __launch_bounds__(64 * WPG) void zfec_bao_fused_kernel(FusedArgs a) {
-    zfec_bao_fused_body<NT, FULL, ORD, DG, KIND, DQ, MP, SS, O32, GFP, WPG, NTL, PRIO, RT>(a);
+template <bool FULL, int KIND = 0, bool O32 = false, int GFP = 0, bool NTL = false>
+__global__ __launch_bounds__(FTPB) void zfec_bao_fused_kernel(FusedArgs a) {
+    zfec_bao_fused_body<FULL, KIND, O32, GFP, NTL>(a);
 }
 
 // K13S (tools/fused_tune only; measured 15-20 % SLOWER than K13, profiles/r7j,
@@ -49,7 +48,7 @@ template <int NPB> constexpr int stpb() { return 64 * (SHW + SHW / NPB); }
 constexpr int STPB = 64 * (SHW + SHW / 2);
 constexpr size_t S_LDS_BYTES = TAB_BYTES + (size_t)SHW * 64 * RW * 4 + 16;
 
-template <bool NT, int NPB = 2>
+template <int NPB = 2>
 __global__ __launch_bounds__(stpb<NPB>()) void zfec_bao_spec_kernel(FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     {
@@ -157,7 +156,7 @@ __global__ __launch_bounds__(stpb<NPB>()) void zfec_bao_spec_kernel(FusedArgs a)
                 const uint32_t x = d + 128u * (st - 1) + 16u * gl;
                 const uint32_t *row = rows + (t * 8 + cu) * RW;
                 const u32x2 lo = piece(row, x), hi = piece(row, x + 8);
-                st16<NT>(L.ob + (uint64_t)(L.lso[t] + x), u32x4{lo.x, lo.y, hi.x, hi.y});
+                st16(L.ob + (uint64_t)(L.lso[t] + x), u32x4{lo.x, lo.y, hi.x, hi.y});
             }
         }
         if (st == 0 || st == 7) {
@@ -186,7 +185,7 @@ __global__ __launch_bounds__(stpb<NPB>()) void zfec_bao_spec_kernel(FusedArgs a)
         }
     };
 
-    Tree<NT> tree(lane, a.cv);
+    Tree tree(lane, a.cv);
     uint32_t *hrows = rows_of(hasher ? wave : 0);
     uint32_t *rX[NPB];
     u32x4 vX[NPB][4];

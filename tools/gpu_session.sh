@@ -46,7 +46,7 @@ for s in "$@"; do
     ftune) run fused_tune 300 ./tools/fused_tune 256 5 ;;
     ftunepmc) run fused_tune_pmc 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU -d $O/ftpmc -o ftpmc --output-format csv -- ./tools/fused_tune 256 1 ;;
     baotune) run bao_tune 300 ./tools/bao_tune 256 32 5 ;;
-    baotunepmc) run bao_tune_fetch 300 rocprofv3 --pmc FETCH_SIZE -d $O/btpmc -o btpmc --output-format csv -- ./tools/bao_tune 256 32 1 1,3 ;;
+    baotunepmc) run bao_tune_fetch 300 rocprofv3 --pmc FETCH_SIZE -d $O/btpmc -o btpmc --output-format csv -- ./tools/bao_tune 256 32 1 1 ;;
     numaprobe) run numa_probe 120 python3 tools/numa_probe.py ;;
     hasherva) for i in 1 2 3; do run bench_hasher_va_$i 300 python3 bench.py --full --mode hasher --steps 3 --warmup 1 --no-cpu-baseline; CHIP_HASHER_VA=0 run bench_hasher_nova_$i 300 python3 bench.py --full --mode hasher --steps 3 --warmup 1 --no-cpu-baseline; done ;;
     hashercopy) for i in 1 2; do run bench_hasher_nt_$i 300 python3 bench.py --full --mode hasher --steps 3 --warmup 1 --no-cpu-baseline; CHIP_NT_COPY=0 run bench_hasher_memcpy_$i 300 python3 bench.py --full --mode hasher --steps 3 --warmup 1 --no-cpu-baseline; CHIP_COPY_THREADS=16 run bench_hasher_nt_t16_$i 300 python3 bench.py --full --mode hasher --steps 3 --warmup 1 --no-cpu-baseline; CHIP_HOST_COPY=direct run bench_hasher_direct_$i 300 python3 bench.py --full --mode hasher --steps 3 --warmup 1 --no-cpu-baseline; done ;;
@@ -95,8 +95,7 @@ for s in "$@"; do
                            run bench_pdec12_soff56_$i 300 python3 bench.py --full --mode pipeline-decode --level 12 --no-cpu-baseline --stream-offset 56; done ;;
     scrubbab) for i in 1 2; do run bench_scrub_batch_soff0_$i 300 python3 bench.py --full --mode scrub-batch --steps 5 --warmup 1 --no-cpu-baseline --stream-offset 0
                            run bench_scrub_batch_soff56_$i 300 python3 bench.py --full --mode scrub-batch --steps 5 --warmup 1 --no-cpu-baseline --stream-offset 56; done ;;
-    ftsoff) for o in 0 56 0 56; do FT_SOFF=$o run fused_tune_soff${o}_$RANDOM 300 ./tools/fused_tune 256 5 "product"; done
-            for o in 0 56; do FT_SOFF=$o run fused_tune_dg_soff$o 300 ./tools/fused_tune 256 5 "K0 DG"; done ;;
+    ftsoff) for o in 0 56 0 56; do FT_SOFF=$o run fused_tune_soff${o}_$RANDOM 300 ./tools/fused_tune 256 5 "product"; done ;;
     crcab) run host_encode_probe 300 ./tools/host_encode_probe 16 4
            for i in 1 2; do run bench_e2e15_full_crc3_$i 400 python3 bench.py --full --config cfg4 --steps 4 --warmup 1 --no-cpu-baseline --no-verify
                            CHIP_CRC_CHAINS=1 run bench_e2e15_full_crc1_$i 400 python3 bench.py --full --config cfg4 --steps 4 --warmup 1 --no-cpu-baseline --no-verify

@@ -71,11 +71,11 @@ struct Variant {
     int bpc, chunk;
 };
 
-template <int U, int MAP, int CH, int WPE>
+template <int U, int CH, int WPE>
 Variant V(int bpc) {
     char buf[64];
-    snprintf(buf, sizeof buf, "U%d MAP%d CH%-3d bpc%d", U, MAP, CH, bpc);
-    return Variant{buf, gf_apply_kernel<4, 1, U, MAP, true, 0, WPE, 0, true>, bpc, CH};
+    snprintf(buf, sizeof buf, "U%d CH%-3d bpc%d", U, CH, bpc);
+    return Variant{buf, gf_apply_kernel<4, 1, U, true, WPE, 0, true>, bpc, CH};
 }
 
 int main(int argc, char **argv) {
@@ -208,7 +208,7 @@ int main(int argc, char **argv) {
     CK(hipMemset(dq, 0, 4096));
     unsigned long long *dsum;
     CK(hipMalloc(&dsum, 8));
-    std::vector<Variant> vs = {V<2, 3, 32, 2>(2), V<2, 6, 32, 2>(2), V<2, 6, 8, 2>(2), V<1, 6, 16, 1>(4)};
+    std::vector<Variant> vs = {V<2, 32, 2>(2), V<2, 8, 2>(2), V<1, 16, 1>(4)};
     uint8_t *in = nullptr, *out = nullptr;
     CK(hipMemAddressReserve(reinterpret_cast<void **>(&in), 16 * GiB, GiB, nullptr, 0));
     CK(hipMemAddressReserve(reinterpret_cast<void **>(&out), 32 * GiB, GiB, nullptr, 0));

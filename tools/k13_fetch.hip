@@ -3,8 +3,9 @@
 // input bytes).  Runs, in one process and in a fixed order, the FULL product
 // kernel at the 16 MiB shape (4096 chunk-columns per shard) and the general
 // product kernel at the 16 MiB shape and at the level-15 shape (4097
-// columns, zfec padding), plus diagnostics (fused_device.hpp DG 1, 3, 5, 11,
-// 12, 13, 14), each `reps` times after one warm-up launch.  Under
+// columns, zfec padding) and at two input row strides, each `reps` times
+// after one warm-up launch (the diagnostics and the run mode that attributed
+// the difference: profiles/NOT_KEPT.md).  Under
 // `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` the dispatches come out
 // in this order; tools/k13_fetch_summary.py pairs them with the labels this
 // prints.  Calibration tool (not product code).
@@ -90,8 +91,6 @@ int main(int argc, char **argv) {
     CK(hbm::Allocator::get().alloc(out_bytes, reinterpret_cast<void **>(&out)));
     const uint64_t cv_bytes = count * 8 * (8 * sh[1].bpo) * 32;  // >= count * N * 32 for both shapes
     CK(hipMalloc(&cv, cv_bytes));
-    uint8_t *cv3;  // run mode: level-3 CVs
-    CK(hipMalloc(&cv3, count * sh[1].N / 8 * 32));
     hipLaunchKernelGGL(fill_kernel, dim3(4096), dim3(256), 0, 0, (uint64_t *)in, in_bytes / 8, 0xCA4B0AD0ull);
     CK(hipMemset(out, 0, out_bytes));
     std::vector<uint8_t> enc = zfec_enc_matrix(4, 8);
@@ -106,29 +105,15 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&dq, 4096));
     CK(hipMemset(dq, 0, 4096));
     using fused::zfec_bao_fused_kernel;
-    // the product's template arguments (fused_kernels.hip KF32 / KG32), DG varied
+    // the product's template arguments (fused_kernels.hip KF32 / KG32)
     const std::vector<Variant> vs = {
-        {"FULL product @16MiB", zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 1>, 0, true},
-        {"general product @16MiB", zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 1, 0, true, 1>, 0, false},
-        {"general product @L15", zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 1, 0, true, 1>, 1, false},
-        {"general DG13 no level-0 CV stores @L15", zfec_bao_fused_kernel<true, false, 1, 13, 0, true, 1, 0, true, 1>, 1, false},
-        {"general DG14 block-padded CV layout @L15", zfec_bao_fused_kernel<true, false, 1, 14, 0, true, 1, 0, true, 1>, 1, false},
-        {"general DG12 node slots zero-filled @L15", zfec_bao_fused_kernel<true, false, 1, 12, 0, true, 1, 0, true, 1>, 1, false},
-        {"general DG5 aligned lines @L15", zfec_bao_fused_kernel<true, false, 1, 5, 0, true, 1, 0, true, 1>, 1, false},
-        {"general DG1 no line stores @L15", zfec_bao_fused_kernel<true, false, 1, 1, 0, true, 1, 0, true, 1>, 1, false},
-        {"general DG3 no GF @L15", zfec_bao_fused_kernel<true, false, 1, 3, 0, true, 1, 0, true, 1>, 1, false},
-        {"FULL DG11 no tree node stores @16MiB", zfec_bao_fused_kernel<true, true, 1, 11, 0, true, 0, 0, true, 1>, 0, true},
-        {"general DG13 no level-0 CV stores @16MiB", zfec_bao_fused_kernel<true, false, 1, 13, 0, true, 1, 0, true, 1>, 0, false},
-        {"general DG14 block-padded CV layout @16MiB", zfec_bao_fused_kernel<true, false, 1, 14, 0, true, 1, 0, true, 1>, 0, false},
-        {"general product @L15 16-B rows", zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 1, 0, true, 1>, 2, false},
-        {"FULL product @16MiB+16 rows", zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 1>, 3, true},
-        {"FULL product @16MiB (again)", zfec_bao_fused_kernel<true, true, 1, 0, 0, true, 0, 0, true, 1>, 0, true},
-        {"general product @L15 (again)", zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 1, 0, true, 1>, 1, false},
-        {"general RT16 MP0 @L15 (run mode)", zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 0, 0, true, 1, 8, false, 0, 16>, 1, false},
-        {"general RT16 MP1 @L15", zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 1, 0, true, 1, 8, false, 0, 16>, 1, false},
-        {"general RT8 MP0 @L15", zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 0, 0, true, 1, 8, false, 0, 8>, 1, false},
-        {"general RT32 MP0 @L15", zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 0, 0, true, 1, 8, false, 0, 32>, 1, false},
-        {"general product @L15 (third)", zfec_bao_fused_kernel<true, false, 1, 0, 0, true, 1, 0, true, 1>, 1, false},
+        {"FULL product @16MiB", zfec_bao_fused_kernel<true, 0, true, 1>, 0, true},
+        {"general product @16MiB", zfec_bao_fused_kernel<false, 0, true, 1>, 0, false},
+        {"general product @L15", zfec_bao_fused_kernel<false, 0, true, 1>, 1, false},
+        {"general product @L15 16-B rows", zfec_bao_fused_kernel<false, 0, true, 1>, 2, false},
+        {"FULL product @16MiB+16 rows", zfec_bao_fused_kernel<true, 0, true, 1>, 3, true},
+        {"FULL product @16MiB (again)", zfec_bao_fused_kernel<true, 0, true, 1>, 0, true},
+        {"general product @L15 (again)", zfec_bao_fused_kernel<false, 0, true, 1>, 1, false},
     };
     for (const auto &v : vs)
         CK(hipFuncSetAttribute(reinterpret_cast<const void *>(v.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -146,7 +131,6 @@ int main(int argc, char **argv) {
         a.out = out; a.out_stride = s.out_stride;
         a.count = count; a.N = s.N; a.cols = s.cols; a.bpo = s.bpo;
         a.table = dtab; a.coff = s.coff; a.cv = cv; a.queue = dq; a.cvs = s.N / 8;
-        a.cv3 = cv3;
         if (v.full && (s.cols % 8 || s.n < 4 * s.C)) { fprintf(stderr, "FULL needs cols %% 8 == 0\n"); return 1; }
         const uint64_t blocks = count * s.bpo;
         const unsigned grid = (unsigned)std::min<uint64_t>(256, (blocks + fused::FW - 1) / fused::FW);

@@ -1,4 +1,4 @@
-// stride_probe.hip — the product's 4-of-8 K1 kernel (schedule S0) on one pair
+// stride_probe.hip — the product's 4-of-8 K1 kernel on one pair
 // of big allocations, with the object strides padded and the batch size
 // varied, interleaved in ONE process so that the placement of the buffers in
 // HBM is the same for every case (calibration tool, not product code).
@@ -70,7 +70,10 @@ int main(int argc, char **argv) {
     uint32_t *dtab;
     CK(hipMalloc(&dtab, tab.size() * 4));
     CK(hipMemcpy(dtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-    auto fn = gf_apply_kernel<4, 1, 2, 3, true, 0, 2, 0, true>;  // the product's schedule S0
+    auto fn = gf_apply_kernel<4, 1, 2, true, 2, 0, true>;  // the product's 4-of-8 kernel
+    uint32_t *dq;  // its run-queue counters
+    CK(hipMalloc(&dq, 4096));
+    CK(hipMemset(dq, 0, 4096));
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
@@ -89,6 +92,7 @@ int main(int argc, char **argv) {
             a.total_tiles = a.tiles_per_obj * c.objects;
             a.count = c.objects;
             a.table = dtab;
+            a.queue = dq;
             for (int j = 0; j < ZF_MAXK; ++j) {
                 a.in_off[j] = j < 4 ? j * C : 0;
                 a.copy_off[j] = j < 4 ? j * C : NO_OUT;

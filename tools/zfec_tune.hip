@@ -55,12 +55,12 @@ struct Variant {
     bool bl = false;
 };
 
-template <int U, int MAP, bool NT, int CH = 1, int WPE = 1, int SB = 0, bool PF = false, bool NTL = false>
+template <int U, bool NT, int CH = 1, int WPE = 1, int SB = 0, bool PF = false, bool NTL = false>
 Variant V(int bpc) {
     char buf[96];
-    snprintf(buf, sizeof buf, "U%d MAP%d CH%-3d wpe%d sb%d pf%d ntl%d %s bpc%d", U, MAP, CH, WPE, SB, PF, NTL,
-             NT ? "nt " : "pln", bpc);
-    return Variant{buf, gf_apply_kernel<4, 1, U, MAP, NT, 0, WPE, SB, PF, NTL>, bpc, CH, (size_t)256 * 4 * 8 * 4};
+    snprintf(buf, sizeof buf, "U%d CH%-3d wpe%d sb%d pf%d ntl%d %s bpc%d", U, CH, WPE, SB, PF, NTL, NT ? "nt " : "pln",
+             bpc);
+    return Variant{buf, gf_apply_kernel<4, 1, U, NT, WPE, SB, PF, NTL>, bpc, CH, (size_t)256 * 4 * 8 * 4};
 }
 
 // bao-layout kernel (encode() Zfec|Bao): chunk slots of a bao stream, wave runs of CH 1 KiB units
@@ -72,12 +72,12 @@ Variant VBL(int bpc) {
     return Variant{buf, gf_apply_bl_kernel<NT, BL>, bpc, CH, (size_t)256 * 4 * 8 * 4, BL};
 }
 
-// 8-of-16 variants (K = 8, NG = 2), replica count R
-template <int U, int MAP, bool NT, int R, int CH = 1, int WPE = 1, int SB = 0, bool PF = false>
+// 8-of-16 variants (K = 8, NG = 2)
+template <int U, bool NT, int CH = 1, int WPE = 1, int SB = 0, bool PF = false>
 Variant V16(int bpc) {
     char buf[80];
-    snprintf(buf, sizeof buf, "8of16 U%d MAP%d CH%-3d R%d wpe%d sb%d pf%d %s bpc%d", U, MAP, CH, R, WPE, SB, PF, NT ? "nt " : "pln", bpc);
-    return Variant{buf, gf_apply_kernel<8, 2, U, MAP, NT, R, WPE, SB, PF>, bpc, CH, (size_t)256 * 8 * R * 8};
+    snprintf(buf, sizeof buf, "8of16 U%d CH%-3d wpe%d sb%d pf%d %s bpc%d", U, CH, WPE, SB, PF, NT ? "nt " : "pln", bpc);
+    return Variant{buf, gf_apply_kernel<8, 2, U, NT, WPE, SB, PF>, bpc, CH, (size_t)256 * 8 * replicas_for(8) * 8};
 }
 
 int main(int argc, char **argv) {
@@ -124,20 +124,24 @@ int main(int argc, char **argv) {
     a.tiles_per_obj = C / TILE; a.total_tiles = a.tiles_per_obj * count; a.count = count;
     a.out_stride = M * C;
     a.table = dtab;
+    uint32_t *dq;  // run-queue counters (QueueIter): zero at launch, left zero
+    CK(hipMalloc(&dq, 4096));
+    CK(hipMemset(dq, 0, 4096));
+    a.queue = dq;
     for (int j = 0; j < ZF_MAXK; ++j) { a.in_off[j] = j < K ? j * C : 0; a.copy_off[j] = j < K ? j * C : NO_OUT; }
     for (int q = 0; q < ZF_MAXP; ++q) a.par_off[q] = q < K ? (K + q) * C : NO_OUT;
 
     std::vector<Variant> vs;
     if (K == 4)
-        vs = {V<2, 3, true, 32, 2, 0, true>(2),  V<1, 3, true, 64, 1, 0, true>(4),  V<2, 3, true, 32, 2, 0, true>(1),
-              V<2, 3, false, 32, 2, 0, true>(2), V<1, 3, false, 64, 1, 0, true>(4), V<2, 3, false, 32, 2, 0, true>(1),
-              V<2, 3, true, 16, 2, 0, true>(1),  V<2, 3, true, 64, 2, 0, true>(1)};
+        vs = {V<2, true, 32, 2, 0, true>(2),  V<1, true, 64, 1, 0, true>(4),  V<2, true, 32, 2, 0, true>(1),
+              V<2, false, 32, 2, 0, true>(2), V<1, false, 64, 1, 0, true>(4), V<2, false, 32, 2, 0, true>(1),
+              V<2, true, 16, 2, 0, true>(1),  V<2, true, 64, 2, 0, true>(1)};
     else
-        vs = {V16<1, 3, true, 4, 64>(1),                V16<1, 3, true, 4, 64, 2, 1, true>(2),
-              V16<1, 3, true, 4, 64, 2, 1, true>(1),    V16<1, 3, true, 4, 64, 1, 0, true>(1),
-              V16<1, 3, true, 4, 64, 2, 2, true>(2),    V16<1, 3, true, 4, 16, 2, 1, true>(2),
-              V16<1, 3, true, 4, 64, 3, 1>(2),          V16<1, 3, false, 4, 64, 2, 1, true>(2),
-              V16<1, 3, false, 4, 64, 2, 1, true>(1),   V16<1, 3, false, 4, 32, 2, 1, true>(2)};
+        vs = {V16<1, true, 64>(1),                V16<1, true, 64, 2, 1, true>(2),
+              V16<1, true, 64, 2, 1, true>(1),    V16<1, true, 64, 1, 0, true>(1),
+              V16<1, true, 64, 2, 2, true>(2),    V16<1, true, 16, 2, 1, true>(2),
+              V16<1, true, 64, 3, 1>(2),          V16<1, false, 64, 2, 1, true>(2),
+              V16<1, false, 64, 2, 1, true>(1),   V16<1, false, 32, 2, 1, true>(2)};
     unsigned long long *dsum;
     CK(hipMalloc(&dsum, 8));
     std::vector<std::vector<float>> ms(vs.size());

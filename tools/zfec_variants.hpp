@@ -9,10 +9,10 @@
 namespace chip {
 namespace zf {
 
-template <int K, int NG, int U, int MAP, bool NT, int RO = 0, int WPE = 1, int SB = 0, bool PF = false,
-          bool NTL = false, bool TR = false>
+// WPE: the waves-per-EU hint of the kernel (the body does not see it)
+template <int K, int NG, int U, bool NT, int WPE = 1, int SB = 0, bool PF = false, bool NTL = false>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(WPE))) void gf_apply_kernel(ApplyArgs a) {
-    gf_apply_body<K, NG, U, MAP, NT, RO, WPE, SB, PF, NTL, TR>(a);
+    gf_apply_body<K, NG, U, NT, SB, PF, NTL>(a);
 }
 
 }  // namespace zf
