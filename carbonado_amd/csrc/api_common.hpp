@@ -13,11 +13,15 @@
 //                      copies, library info, sizes, batch-buffer allocation
 //   api_host_copy.cpp  host <-> HBM copies (pinned ring, copy threads, NUMA)
 //   api_plans.cpp      zfec plans, encode() at Zfec|Bao on the device, bao
-//                      and slice geometry, EncodeInfo, host-stage glue
+//                      and slice geometry, host-stage glue
+//   hostbatch_plan.hpp the planning arithmetic of the three below (pure host
+//                      code): the host-made region of a stream, slice sizing,
+//                      encode's bounds and EncodeInfo, decode's geometry
 //   api_stages.cpp     the stage functions and the device-resident batches
 //   api_scrub.cpp      verify_slice / extract_slice / scrub (single, batch)
 //   api_encode.cpp     encode() from host memory (single, host batch)
 //   api_decode.cpp     decode() from host memory (single, host batch)
+//   api_single.cpp     one object from host memory on KM / KS, zero-copy
 //   api_hasher.cpp     the streaming BaoHasher
 #pragma once
 
@@ -38,6 +42,7 @@
 #include "chip_internal.hpp"
 #include "gf256.hpp"
 #include "host_stages.hpp"
+#include "hostbatch_plan.hpp"
 #include "stream_rules.hpp"
 
 #define CHIP_HIP(expr)                                  \
@@ -64,8 +69,12 @@ struct DevBuf {
     size_t cap = 0;
 };
 
-// one pipeline slot of chip_encode_host_batch: its own stream and buffers
-// (`stage` is pinned host memory holding the host-stage output of a slice)
+// one pipeline slot of chip_encode_host_batch / chip_decode_host_batch: its
+// own stream and buffers.  `stage` is pinned host memory: the host-stage
+// output of an encode's slice, or what a decode's slice hands its host stages
+// (then the per-object status words); `nodes` / `hnodes` the compact parent
+// nodes of the streams' host-made regions (hostbatch::HostGeo), on the device
+// and pinned
 struct Slot {
     hipStream_t stream = nullptr;
     DevBuf in, mid, out, hash, scratch, nodes, sin;  // sin: data regions taken from host rows
@@ -154,6 +163,7 @@ inline uint64_t row_pitch(uint64_t n) { return (n + 255) / 256 * 256; }
 
 // ---- plans and geometry (api_plans.cpp) ------------------------------------
 int env_int(const char *name, int dflt);
+bool env_default_on(const char *name);  // a knob that only the value "0" turns off
 bool valid_km(uint32_t k, uint32_t m);
 void calc_pad(uint64_t n, uint32_t k, uint32_t *pad, uint64_t *C);  // utils.rs:47-58, k generalised
 // rows 0..k-1 copied, k..m-1 computed (aliased: in place, parity rows only)
@@ -179,9 +189,10 @@ struct SliceNode {
     uint64_t off, len, index;  // stream offset, bytes, chunk index or parent index (stream order)
 };
 void slice_nodes(uint64_t n, uint64_t c0, uint64_t c1, std::vector<SliceNode> *out);
-int encode_info_for(uint8_t format, uint64_t input_len, uint64_t cur, uint64_t bc, uint64_t be,
-                    chip_encode_info *inf, uint64_t *zlen, uint64_t *final_len);
-bool has_host_stages(uint8_t format);
+using hostbatch::encode_info_for;
+using hostbatch::has_host_stages;
+using hostbatch::host_stage_max;
+using hostbatch::bao_header;
 
 // grow-only, uninitialised host scratch (std::vector::resize would zero-fill
 // and page-fault 16 MiB per object)
@@ -198,11 +209,13 @@ struct Scratch {
 };
 
 bool stream_encrypt_on();
-uint64_t host_stage_max(uint8_t format, uint64_t n);
 int host_stages_into(uint8_t format, const uint8_t *pk, uint64_t pklen, const uint8_t *eph, const uint8_t *nonce,
                      const uint8_t *in, uint64_t n, uint8_t *dst, uint64_t cap, Scratch &tmp,
                      uint64_t *len, uint64_t *bc, uint64_t *be, const host::ChunkSink *sink = nullptr,
                      uint64_t *filled = nullptr, const host::EciesKey *prepared = nullptr, bool par = false);
+
+// fn(t) for t < nt on the caller and nt - 1 fresh threads (a host batch's slice)
+void run_threads(uint32_t nt, const std::function<void(uint32_t)> &fn);
 
 // ---- one object from host memory on KM (api_single.cpp) ---------------------
 // CHIP_SINGLE_TRACE=1: the host-side phases of each call to stderr (us)
@@ -274,17 +287,10 @@ bool bao_content_len(uint64_t len, uint64_t *n);
 int bao_encode_ctx(Ctx *c, const uint8_t *d_in, uint64_t n, bool want_stream, uint8_t hash[32]);
 int bao_decode_ctx(Ctx *c, const uint8_t *d_enc, uint64_t len, uint64_t n, const uint8_t *hash, uint8_t *d_dst,
                    uint64_t out_limit = ~0ull, uint32_t *deferred = nullptr);
-int bao_header(const uint8_t *enc, uint64_t len, uint64_t *n);
 int node_check_ctx(Ctx *c, uint64_t n, const uint8_t *hash, std::vector<uint8_t> *cf, std::vector<uint8_t> *pf);
 bool slice_ok(uint64_t n, uint64_t c0, uint64_t c1, const std::vector<uint8_t> &cf, const std::vector<uint8_t> &pf);
 int scrub_repair_enqueue(Ctx *c, const uint8_t *d_stream, uint64_t n, uint64_t len, const std::vector<uint32_t> &good,
                          uint32_t padding, uint64_t C, uint8_t *d_dst, uint8_t *d_h2);
-
-// A zfec batch: one launch (the dynamic run queue balances the XCDs inside it).
-template <typename F>  // launch(o0, cnt, stream) -> hipError_t, objects [o0, o0 + cnt)
-hipError_t zf_run(uint64_t count, hipStream_t s, F launch) {
-    return launch(0, count, s);
-}
 
 }  // namespace api
 }  // namespace chip

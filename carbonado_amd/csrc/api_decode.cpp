@@ -1,7 +1,7 @@
 // api_decode.cpp — decode() from host memory (decoding.rs:80-114): one
 // object (chip_decode) and the pipelined host batch (chip_decode_host_batch:
 // H2D, bao verify-decode, D2H, host stages on host threads).  Shared
-// declarations: api_common.hpp.
+// declarations: api_common.hpp; the geometry: hostbatch_plan.hpp.
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -13,16 +13,13 @@ using namespace chip::api;
 
 namespace {
 
-// device-stage geometry of one encoded object (decoding.rs:80-99)
-struct DecGeom {
-    int st = CHIP_OK;
-    uint64_t blen = 0;  // bytes entering zfec (bao content length, or the input length)
-    uint64_t olen = 0;  // bytes leaving zfec (k*C - padding, or blen)
-};
+using hostbatch::DecGeom;
 
 // decode()'s host stages (decoding.rs:101-111) on the device stages' output
-// cur[0, cur_n): ECIES (with the key derived ahead, when there is one) then
-// snappy, or the two in one pass; a large object on the stage pool.
+// cur[0, cur_n) of ONE object: ECIES then snappy, or the two in one pass.
+// The pooled implementations with the key derived ahead (when there is one):
+// the caller's only object may take every thread of the stage pool, and its
+// key was derived while the device verified.
 int host_tail(const uint8_t *secret_key, uint64_t sk_len, bool ecies, bool snap, const uint8_t *cur, uint64_t cur_n,
               uint8_t *out, uint64_t out_cap, uint64_t *out_len, const uint8_t *pre_key, const uint8_t *pre_eph) {
     Trace trace("host stages");
@@ -51,149 +48,140 @@ bool dec_spec_on() {
     return on;
 }
 
-DecGeom dec_geom(uint8_t format, const uint8_t *in, uint64_t n, uint32_t padding) {
-    DecGeom g;
-    const bool zfec = format & CHIP_FORMAT_ZFEC, bao = format & CHIP_FORMAT_BAO;
-    g.blen = n;
-    if (bao) {
-        g.st = bao_header(in, n, &g.blen);
-        if (g.st != CHIP_OK) return g;
+// Between the thread that enqueues a decode batch's slices and the finisher
+// that completes them in order: how many slices each has done, and whether
+// either gave up.
+struct Handshake {
+    std::mutex m;
+    std::condition_variable cv;
+    uint64_t enqueued = 0, finished = 0;
+    bool aborted = false;
+    // until slice i is enqueued; false: it never will be
+    bool wait_enqueued(uint64_t i) {
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return enqueued > i || aborted; });
+        return enqueued > i;
     }
-    g.olen = g.blen;
-    if (zfec) {
-        if (g.blen % CHIP_FEC_M) { g.st = CHIP_ERR_UNEVEN_ZFEC_CHUNKS; return g; }  // decoding.rs:39-41
-        const uint64_t C = g.blen / CHIP_FEC_M;
-        if (padding > CHIP_FEC_K * C) { g.st = CHIP_ERR_ZFEC; return g; }
-        g.olen = CHIP_FEC_K * C - padding;
+    // until slice i is finished; false: the run is aborted
+    bool wait_finished(uint64_t i) {
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return finished > i || aborted; });
+        return !aborted;
     }
-    return g;
-}
+    // slice i through `step` (enqueued or finished), or with !ok the end of the run; false: the run is aborted
+    bool publish(uint64_t &step, uint64_t i, bool ok) {
+        std::lock_guard<std::mutex> lk(m);
+        if (ok) step = i + 1;
+        else aborted = true;
+        cv.notify_all();
+        return !aborted;
+    }
+};
 
-}  // namespace
+struct DecodeArgs {  // of chip_decode_host_batch, checked
+    uint8_t format;
+    const uint8_t *secret_key; uint64_t sk_len;
+    const uint8_t *hashes, *in; const uint64_t *in_len; uint64_t count, in_stride; const uint32_t *padding;
+    uint8_t *out; uint64_t out_stride, *out_len; int32_t *status;
+};
 
-extern "C" {
-
-int chip_decode_host_batch(uint8_t format, const uint8_t *secret_key, uint64_t sk_len, const uint8_t *hashes,
-                           const uint8_t *in, const uint64_t *in_len, uint64_t count, uint64_t in_stride,
-                           const uint32_t *padding, uint8_t *out, uint64_t out_stride, uint64_t *out_len,
-                           int32_t *status, uint32_t nslots, uint64_t slice_bytes, uint32_t host_threads) {
-    if (count == 0) return CHIP_OK;
-    if (!in || !in_len || !out_len || !status || !padding) return CHIP_ERR_INVALID_ARG;
-    const bool zfec = format & CHIP_FORMAT_ZFEC, bao = format & CHIP_FORMAT_BAO;
-    const bool hs = has_host_stages(format);
-    if ((format & CHIP_FORMAT_ECIES) && !secret_key) return CHIP_ERR_INVALID_ARG;
-    if (bao && !hashes) return CHIP_ERR_HASH_DECODE;
-    // host-side geometry and the largest sizes
-    std::vector<DecGeom> geo(count);
+// One chip_decode_host_batch call: geometry, then either host_only, or plan,
+// prepare_slots and run (enqueue on this thread, finish on the finisher's).
+struct DecodeBatch : DecodeArgs {
+    const bool zfec = format & CHIP_FORMAT_ZFEC, bao = format & CHIP_FORMAT_BAO, hs = has_host_stages(format);
+    const bool ecies = format & CHIP_FORMAT_ECIES, snap = format & CHIP_FORMAT_SNAPPY;
+    std::vector<DecGeom> geo;
     uint64_t in_max = 0, mid_max = 0, olen_max = 0;
-    for (uint64_t o = 0; o < count; ++o) {
-        geo[o] = dec_geom(format, in + o * in_stride, in_len[o], padding[o]);
-        status[o] = geo[o].st;
-        in_max = std::max(in_max, in_len[o]);
-        mid_max = std::max(mid_max, geo[o].blen);
-        olen_max = std::max(olen_max, geo[o].olen);
-    }
-    if (!zfec && !bao) {  // host stages only (or identity)
+    Ctx *c = nullptr;
+    hostbatch::Slices p{};
+    uint64_t i_al = 0, m_al = 0, o_al = 0;  // pitches: slot input rows, bao's output rows, the pinned stage's rows
+    std::vector<Scratch> dscratch;          // per host thread, reused across slices
+    Handshake hsk;
+    std::string fin_err;
+
+    // host-side geometry and the largest sizes
+    void geometry() {
+        geo.resize(count);
         for (uint64_t o = 0; o < count; ++o) {
-            if (status[o] != CHIP_OK) continue;
-            const uint8_t *src = in + o * in_stride;
-            uint64_t n = in_len[o];
-            uint8_t *dst = out + o * out_stride;
-            if (!hs) {
-                if (n > out_stride && count > 1) { status[o] = CHIP_ERR_BUFFER_TOO_SMALL; out_len[o] = n; continue; }
-                std::memcpy(dst, src, n);
-                out_len[o] = n;
-                continue;
-            }
-            uint64_t got = 0;
-            int st = CHIP_OK;
-            if ((format & CHIP_FORMAT_ECIES) && (format & CHIP_FORMAT_SNAPPY)) {
-                st = host::ecies_decrypt_snap_par(secret_key, sk_len, src, n, dst, out_stride, &got);
-            } else if (format & CHIP_FORMAT_ECIES) {  // Ecies alone here (Ecies|Snappy above)
-                st = host::ecies_decrypt_par(secret_key, sk_len, src, n, dst, out_stride, &got);
-            }
-            else if (format & CHIP_FORMAT_SNAPPY) st = host::snap_decompress(src, n, dst, out_stride, &got);
-            status[o] = st;
-            out_len[o] = got;
+            geo[o] = hostbatch::dec_geom(format, in + o * in_stride, in_len[o], padding[o]);
+            status[o] = geo[o].st;
+            in_max = std::max(in_max, in_len[o]);
+            mid_max = std::max(mid_max, geo[o].blen);
+            olen_max = std::max(olen_max, geo[o].olen);
         }
+    }
+
+    int first_error() const {
         for (uint64_t o = 0; o < count; ++o)
             if (status[o] != CHIP_OK) return status[o];
         return CHIP_OK;
     }
-    Ctx *c;
-    int st = ctx_get(&c);
-    if (st != CHIP_OK) return st;
-    nslots = nslots < 1 ? 3 : (nslots > 8 ? 8 : nslots);
-    if (slice_bytes == 0) slice_bytes = 256ull << 20;
-    uint32_t T = host_threads ? host_threads : std::max(1u, std::thread::hardware_concurrency());
-    T = std::min<uint32_t>(T, 64);
-    const uint64_t i_al = row_pitch(in_max), m_al = row_pitch(mid_max), o_al = (olen_max + 15) / 16 * 16;
-    uint64_t S = slice_bytes / (in_max ? in_max : 1);
-    S = S < 1 ? 1 : (S > count ? count : S);
-    if (c->slots.size() < nslots) c->slots.resize(nslots);
-    for (uint32_t k = 0; k < nslots; ++k) {
-        Slot &sl = c->slots[k];
-        if (!sl.stream) CHIP_HIP(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-        CHIP_HIP(grow(sl.in, S * i_al));
-        if (bao) {
-            CHIP_HIP(grow(sl.mid, S * m_al));
-            CHIP_HIP(grow(sl.scratch, bao_scratch_len(mid_max, S)));
-            CHIP_HIP(grow(sl.hash, S * 32 + S * 4));  // hashes, then per-object status words
-        }
-        if (hs) CHIP_HIP(grow_pinned(sl.stage, S * o_al + S * 4));
-        else if (bao) CHIP_HIP(grow_pinned(sl.stage, S * 4));
-    }
-    const uint64_t nslices = (count + S - 1) / S;
-    std::vector<Scratch> dscratch(T);  // per host thread, reused across slices
-    // host part of slice i: device statuses -> status[], then ecies -> snap into out
-    auto finish = [&](uint64_t i) {
-        Slot &sl = c->slots[i % nslots];
-        const uint64_t o0 = i * S, cnt = std::min(S, count - o0);
-        const uint8_t *stage = static_cast<const uint8_t *>(sl.stage.p);
-        const uint32_t *dst_st = reinterpret_cast<const uint32_t *>(stage + (hs ? S * o_al : 0));
-        for (uint64_t j = 0; j < cnt; ++j)
-            if (bao && status[o0 + j] == CHIP_OK && dst_st[j]) status[o0 + j] = (int32_t)dst_st[j];
-        if (!hs) return;
-        const uint32_t nt = (uint32_t)std::min<uint64_t>(T, cnt);
-        auto work = [&](uint32_t t) {
-            Scratch &tmp = dscratch[t];
-            for (uint64_t j = t; j < cnt; j += nt) {
-                const uint64_t o = o0 + j;
-                if (status[o] != CHIP_OK) continue;
-                const uint8_t *src = stage + j * o_al;
-                uint64_t n = geo[o].olen, got = 0;
-                uint8_t *dst = out + o * out_stride;
-                int r = CHIP_OK;
-                if ((format & CHIP_FORMAT_ECIES) && (format & CHIP_FORMAT_SNAPPY)) {  // one pass, no plaintext buffer
-                    status[o] = host::ecies_decrypt_snap(secret_key, sk_len, src, n, dst, out_stride, &got,
-                                                         tmp.get(host::DECRYPT_SNAP_WINDOW));
-                    out_len[o] = got;
-                    continue;
-                }
-                if (format & CHIP_FORMAT_ECIES) {
-                    const bool snap = format & CHIP_FORMAT_SNAPPY;
-                    uint8_t *tb = snap ? tmp.get(n + 1) : nullptr;
-                    r = host::ecies_decrypt(secret_key, sk_len, src, n, snap ? tb : dst, snap ? n + 1 : out_stride,
-                                            &got);
-                    src = tb;
-                    n = got;
-                }
-                if (r == CHIP_OK && (format & CHIP_FORMAT_SNAPPY)) r = host::snap_decompress(src, n, dst, out_stride, &got);
-                status[o] = r;
-                out_len[o] = got;
+
+    // No Zfec/Bao bit: host stages only (or identity), the objects one after the
+    // other on this thread.  The pooled implementations without a key derived
+    // ahead: each object in its turn may take the stage pool, and there is no
+    // device stage during which its key could have been derived.
+    int host_only() {
+        for (uint64_t o = 0; o < count; ++o) {
+            if (status[o] != CHIP_OK) continue;
+            const uint8_t *src = in + o * in_stride;
+            const uint64_t n = in_len[o];
+            uint8_t *dst = out + o * out_stride;
+            uint64_t got = n;
+            if (!hs) {
+                if (n > out_stride && count > 1) status[o] = CHIP_ERR_BUFFER_TOO_SMALL;
+                else std::memcpy(dst, src, n);
+            } else {
+                got = 0;
+                if (ecies && snap)
+                    status[o] = host::ecies_decrypt_snap_par(secret_key, sk_len, src, n, dst, out_stride, &got);
+                else if (ecies) status[o] = host::ecies_decrypt_par(secret_key, sk_len, src, n, dst, out_stride, &got);
+                else status[o] = host::snap_decompress(src, n, dst, out_stride, &got);
             }
-        };
-        std::vector<std::thread> pool;
-        for (uint32_t t = 1; t < nt; ++t) pool.emplace_back(work, t);
-        work(0);
-        for (auto &th : pool) th.join();
-    };
+            out_len[o] = got;
+        }
+        return first_error();
+    }
+
+    int plan(uint32_t nslots, uint64_t slice_bytes, uint32_t host_threads) {
+        const int st = ctx_get(&c);
+        if (st != CHIP_OK) return st;
+        p = hostbatch::plan_slices(nslots, slice_bytes, host_threads, std::thread::hardware_concurrency(), in_max, count,
+                                   false);
+        i_al = row_pitch(in_max), m_al = row_pitch(mid_max), o_al = rules::up16(olen_max);
+        dscratch.resize(p.T);
+        return CHIP_OK;
+    }
+
+    int prepare_slots() {
+        const uint64_t S = p.S;
+        if (c->slots.size() < p.nslots) c->slots.resize(p.nslots);
+        for (uint32_t k = 0; k < p.nslots; ++k) {
+            Slot &sl = c->slots[k];
+            if (!sl.stream) CHIP_HIP(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
+            CHIP_HIP(grow(sl.in, S * i_al));
+            if (bao) {
+                CHIP_HIP(grow(sl.mid, S * m_al));
+                CHIP_HIP(grow(sl.scratch, bao_scratch_len(mid_max, S)));
+                CHIP_HIP(grow(sl.hash, S * 32 + S * 4));  // hashes, then per-object status words
+            }
+            if (hs) CHIP_HIP(grow_pinned(sl.stage, S * o_al + S * 4));
+            else if (bao) CHIP_HIP(grow_pinned(sl.stage, S * 4));
+        }
+        return CHIP_OK;
+    }
+
+    // the status words of a slot's slice in its pinned stage (behind the rows of the host stages' input)
+    uint32_t *stage_status(Slot &sl) const {
+        return reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(sl.stage.p) + (hs ? p.S * o_al : 0));
+    }
+
     // device part of slice i (H2D, bao verify, D2H) enqueued on its slot's stream
-    auto enqueue = [&](uint64_t i) -> int {
-        Slot &sl = c->slots[i % nslots];
-        const uint64_t o0 = i * S, cnt = std::min(S, count - o0);
+    int enqueue(uint64_t i) {
+        Slot &sl = c->slots[i % p.nslots];
+        const uint64_t S = p.S, o0 = i * S, cnt = std::min(S, count - o0);
         uint8_t *stage = static_cast<uint8_t *>(sl.stage.p);
-        uint32_t *h_st = reinterpret_cast<uint32_t *>(stage + (hs ? S * o_al : 0));
+        uint32_t *h_st = stage_status(sl);
         for (uint64_t j = 0; j < cnt; ++j) { h_st[j] = 0; if (!hs) out_len[o0 + j] = geo[o0 + j].olen; }
         // uniform slice -> one batched pass; otherwise object by object
         bool uniform = true;
@@ -243,61 +231,98 @@ int chip_decode_host_batch(uint8_t format, const uint8_t *secret_key, uint64_t s
             }
         }
         return CHIP_OK;
-    };
+    }
+
+    // Host part of slice i, its slot's stream done: device statuses -> status[],
+    // then ecies -> snap into out, an object per thread on T threads.  The
+    // one-thread implementations with the thread's own scratch: the threads are
+    // already busy with an object each, so the stage pool would only be fought over.
+    void finish(uint64_t i) {
+        Slot &sl = c->slots[i % p.nslots];
+        const uint64_t o0 = i * p.S, cnt = std::min(p.S, count - o0);
+        const uint8_t *stage = static_cast<const uint8_t *>(sl.stage.p);
+        const uint32_t *dst_st = stage_status(sl);
+        for (uint64_t j = 0; j < cnt; ++j)
+            if (bao && status[o0 + j] == CHIP_OK && dst_st[j]) status[o0 + j] = (int32_t)dst_st[j];
+        if (!hs) return;
+        const uint32_t nt = (uint32_t)std::min<uint64_t>(p.T, cnt);
+        run_threads(nt, [&](uint32_t t) {
+            for (uint64_t j = t; j < cnt; j += nt) {
+                const uint64_t o = o0 + j, n = geo[o].olen;
+                if (status[o] != CHIP_OK) continue;
+                const uint8_t *src = stage + j * o_al;
+                uint8_t *dst = out + o * out_stride;
+                uint64_t got = 0;
+                if (ecies && snap)  // one pass, no plaintext buffer
+                    status[o] = host::ecies_decrypt_snap(secret_key, sk_len, src, n, dst, out_stride, &got,
+                                                         dscratch[t].get(host::DECRYPT_SNAP_WINDOW));
+                else if (ecies) status[o] = host::ecies_decrypt(secret_key, sk_len, src, n, dst, out_stride, &got);
+                else status[o] = host::snap_decompress(src, n, dst, out_stride, &got);
+                out_len[o] = got;
+            }
+        });
+    }
+
+    // the finisher's thread: slices in order, each once its slot's stream is done
+    void finisher_loop() {
+        (void)hipSetDevice(c->dev);
+        for (uint64_t i = 0; i < p.nslices && hsk.wait_enqueued(i); ++i) {
+            const hipError_t e = hipStreamSynchronize(c->slots[i % p.nslots].stream);
+            if (e == hipSuccess) finish(i);
+            else fin_err = hipGetErrorString(e);
+            if (!hsk.publish(hsk.finished, i, e == hipSuccess)) return;
+        }
+    }
+
     // A finisher thread completes slices in order (wait for the slot's stream,
     // then the host stages on T threads) while this thread keeps the device
     // queue full; a slot is reused only after its previous slice finished.
-    std::mutex fm;
-    std::condition_variable fcv;
-    uint64_t enqueued = 0, finished = 0;
-    bool abort_run = false;
-    std::string fin_err;
-    std::thread finisher([&] {
-        (void)hipSetDevice(c->dev);
-        for (uint64_t i = 0; i < nslices; ++i) {
-            {
-                std::unique_lock<std::mutex> lk(fm);
-                fcv.wait(lk, [&] { return enqueued > i || abort_run; });
-                if (enqueued <= i) return;
+    int run() {
+        std::thread finisher([this] { finisher_loop(); });
+        int st = CHIP_OK;
+        for (uint64_t i = 0; i < p.nslices && st == CHIP_OK; ++i) {
+            if (i >= p.nslots && !hsk.wait_finished(i - p.nslots)) {
+                st = CHIP_ERR_DEVICE;
+                break;
             }
-            hipError_t e = hipStreamSynchronize(c->slots[i % nslots].stream);
-            if (e == hipSuccess) finish(i);
-            std::lock_guard<std::mutex> lk(fm);
-            if (e != hipSuccess) {
-                fin_err = hipGetErrorString(e);
-                abort_run = true;
-            }
-            finished = i + 1;
-            fcv.notify_all();
-            if (abort_run) return;
+            st = enqueue(i);
+            hsk.publish(hsk.enqueued, i, st == CHIP_OK);
         }
-    });
-    int run_st = CHIP_OK;
-    for (uint64_t i = 0; i < nslices && run_st == CHIP_OK; ++i) {
-        if (i >= nslots) {
-            std::unique_lock<std::mutex> lk(fm);
-            fcv.wait(lk, [&] { return finished > i - nslots || abort_run; });
-            if (abort_run) { run_st = CHIP_ERR_DEVICE; break; }
+        finisher.join();
+        if (!fin_err.empty()) {
+            t_last_err = fin_err;
+            st = CHIP_ERR_DEVICE;
         }
-        run_st = enqueue(i);
-        std::lock_guard<std::mutex> lk(fm);
-        if (run_st == CHIP_OK) enqueued = i + 1;
-        else abort_run = true;
-        fcv.notify_all();
+        hipError_t e = hipSuccess;
+        for (uint32_t k = 0; k < p.nslots; ++k) {
+            const hipError_t ek = hipStreamSynchronize(c->slots[k].stream);
+            if (e == hipSuccess) e = ek;
+        }
+        if (st != CHIP_OK) return st;
+        CHIP_HIP(e);
+        return first_error();
     }
-    finisher.join();
-    if (!fin_err.empty()) {
-        t_last_err = fin_err;
-        run_st = CHIP_ERR_DEVICE;
-    }
-    if (run_st != CHIP_OK) {
-        for (uint32_t k = 0; k < nslots; ++k) (void)hipStreamSynchronize(c->slots[k].stream);
-        return run_st;
-    }
-    for (uint32_t k = 0; k < nslots; ++k) CHIP_HIP(hipStreamSynchronize(c->slots[k].stream));
-    for (uint64_t o = 0; o < count; ++o)
-        if (status[o] != CHIP_OK) return status[o];
-    return CHIP_OK;
+};
+
+}  // namespace
+
+extern "C" {
+
+int chip_decode_host_batch(uint8_t format, const uint8_t *secret_key, uint64_t sk_len, const uint8_t *hashes,
+                           const uint8_t *in, const uint64_t *in_len, uint64_t count, uint64_t in_stride,
+                           const uint32_t *padding, uint8_t *out, uint64_t out_stride, uint64_t *out_len,
+                           int32_t *status, uint32_t nslots, uint64_t slice_bytes, uint32_t host_threads) {
+    if (count == 0) return CHIP_OK;
+    if (!in || !in_len || !out_len || !status || !padding) return CHIP_ERR_INVALID_ARG;
+    if ((format & CHIP_FORMAT_ECIES) && !secret_key) return CHIP_ERR_INVALID_ARG;
+    if ((format & CHIP_FORMAT_BAO) && !hashes) return CHIP_ERR_HASH_DECODE;
+    DecodeBatch db{{format, secret_key, sk_len, hashes, in, in_len, count, in_stride, padding, out, out_stride, out_len,
+                    status}};
+    db.geometry();
+    if (!db.zfec && !db.bao) return db.host_only();
+    int st = db.plan(nslots, slice_bytes, host_threads);
+    if (st == CHIP_OK) st = db.prepare_slots();
+    return st == CHIP_OK ? db.run() : st;
 }
 
 int chip_decode(const uint8_t *secret_key, uint64_t sk_len, const uint8_t *hash, uint64_t hash_len,
@@ -318,20 +343,11 @@ int chip_decode(const uint8_t *secret_key, uint64_t sk_len, const uint8_t *hash,
         ~Wipe() { host::secure_wipe(k, 32); }
     } wipe_pre{pre_key};
     if (zfec || bao) {
-        uint64_t blen = n;
-        if (bao) {
-            if (!hash || hash_len != CHIP_HASH_LEN) return CHIP_ERR_HASH_DECODE;
-            int st = bao_header(in, n, &blen);
-            if (st != CHIP_OK) return st;
-        }
-        uint64_t C = 0, olen = blen;
-        if (zfec) {
-            if (blen % CHIP_FEC_M != 0) return CHIP_ERR_UNEVEN_ZFEC_CHUNKS;  // decoding.rs:39-41
-            C = blen / CHIP_FEC_M;
-            if (padding > CHIP_FEC_K * C) return CHIP_ERR_ZFEC;
-            if (C % 16) return CHIP_ERR_ZFEC;
-            olen = CHIP_FEC_K * C - padding;
-        }
+        if (bao && (!hash || hash_len != CHIP_HASH_LEN)) return CHIP_ERR_HASH_DECODE;
+        const DecGeom g = hostbatch::dec_geom(format, in, n, padding);
+        if (g.st != CHIP_OK) return g.st;
+        const uint64_t blen = g.blen, olen = g.olen, C = zfec ? blen / CHIP_FEC_M : 0;
+        if (C % 16) return CHIP_ERR_ZFEC;
         uint8_t *dst = out;
         if (ecies || snap) {
             t_dev.resize(olen + 1);
@@ -343,17 +359,18 @@ int chip_decode(const uint8_t *secret_key, uint64_t sk_len, const uint8_t *hash,
         Ctx *c;
         int st = ctx_get(&c);
         if (st != CHIP_OK) return st;
+        // While the device works: the ECIES key from the envelope header as the
+        // input holds it at h0 (content bytes [0, 65): chunk 0 of the bao stream, or
+        // the first shard); decrypt uses it only if the verified header is the same
+        // (the pool path and the one-thread paths alike, so it is never paid twice)
+        const uint64_t h0 = ecies && bao ? bao_chunk_offset(0, (blen + 1023) / 1024) : 0;
+        auto prekey = [&](uint64_t at) {
+            if (!ecies || at + 65 > n || (bao && blen < 65)) return;
+            std::memcpy(pre_eph, in + at, 65);
+            have_pre = host::ecies_derive_key(secret_key, sk_len, pre_eph, pre_key) == CHIP_OK;
+        };
         if (bao && single_ok(blen)) {  // KM / KS verifies; the host gathers [0, olen) from `in` meanwhile
             // (at Bao|Zfec the positional shares' primaries are the content's first 4 C bytes)
-            // while the device verifies, also the ECIES key from the envelope header as `in` holds it
-            auto prekey = [&] {
-                if (!ecies) return;
-                const uint64_t h0 = bao_chunk_offset(0, (blen + 1023) / 1024);
-                if (h0 + 65 <= n && blen >= 65) {
-                    std::memcpy(pre_eph, in + h0, 65);
-                    have_pre = host::ecies_derive_key(secret_key, sk_len, pre_eph, pre_key) == CHIP_OK;
-                }
-            };
             // and then the host stages themselves on the gathered (still unverified) content,
             // into `out`: released only with the device's verdict, wiped without it
             int spec = -1;
@@ -362,29 +379,20 @@ int chip_decode(const uint8_t *secret_key, uint64_t sk_len, const uint8_t *hash,
                 if (!(ecies || snap) || !dec_spec_on() || (ecies && !have_pre)) return;
                 spec = host_tail(secret_key, sk_len, ecies, snap, dst, olen, out, out_cap, out_len, pre_key, pre_eph);
             };
-            st = single_decode_km(c, in, n, blen, hash, dst, olen, prekey, stages);
+            st = single_decode_km(c, in, n, blen, hash, dst, olen, [&] { prekey(h0); }, stages);
             if (spec >= 0) {
                 if (st == CHIP_OK) return spec;
                 if (out && out_cap) host::secure_wipe(out, spec == CHIP_OK ? *out_len : out_cap);
                 *out_len = out_len0;
             }
             if (st != CHIP_OK) return st;
-            cur = dst;
-            cur_n = olen;
         } else if (zfec && !bao && C && zc_ok(2 * CHIP_FEC_K * C)) {  // decoding.rs:95-99: shards by position
             // zero-copy: the decode kernel reads the four primaries from pinned memory
-            auto prekey = [&] {
-                if (!ecies || n < 65) return;
-                std::memcpy(pre_eph, in, 65);
-                have_pre = host::ecies_derive_key(secret_key, sk_len, pre_eph, pre_key) == CHIP_OK;
-            };
             const uint8_t *sh[CHIP_FEC_K];
             std::vector<uint32_t> sel(CHIP_FEC_K);
             for (uint32_t s = 0; s < CHIP_FEC_K; ++s) { sh[s] = in + s * C; sel[s] = s; }
-            st = single_zfec_decode_zc(c, CHIP_FEC_K, CHIP_FEC_M, sh, sel, C, dst, olen, prekey);
+            st = single_zfec_decode_zc(c, CHIP_FEC_K, CHIP_FEC_M, sh, sel, C, dst, olen, [&] { prekey(0); });
             if (st != CHIP_OK) return st;
-            cur = dst;
-            cur_n = olen;
         } else {
             const uint64_t in_bytes = bao ? bao_encoded_len(blen) : n;
             CHIP_HIP(grow(c->in, in_bytes));
@@ -413,26 +421,16 @@ int chip_decode(const uint8_t *secret_key, uint64_t sk_len, const uint8_t *hash,
                 if (st != CHIP_OK) return st;
                 d_cur = static_cast<const uint8_t *>(c->out.p);
             }
-            // While the device verifies: the ECIES key from the envelope header as the
-            // input holds it (content bytes [0, 65): chunk 0 of the bao stream, or the
-            // first shard); decrypt uses it only if the verified header is the same
-            // (the pool path and the one-thread paths alike, so it is never paid twice)
-            if (ecies) {
-                const uint64_t h0 = bao ? bao_chunk_offset(0, (blen + 1023) / 1024) : 0;
-                if (h0 + 65 <= n && (!bao || blen >= 65)) {
-                    std::memcpy(pre_eph, in + h0, 65);
-                    have_pre = host::ecies_derive_key(secret_key, sk_len, pre_eph, pre_key) == CHIP_OK;
-                }
-            }
+            prekey(h0);
             if (olen) CHIP_HIP(d2h(c->stage, dst, d_cur, olen, c->stream));
             CHIP_HIP(small_sync(c));
             if (verdict) {  // never hand back unverified content
                 if (olen) std::memset(dst, 0, olen);
                 return (int)verdict;
             }
-            cur = dst;
-            cur_n = olen;
         }
+        cur = dst;
+        cur_n = olen;
     }
     if (!ecies && !snap) {
         if (!(zfec || bao)) {

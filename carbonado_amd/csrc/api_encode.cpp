@@ -116,98 +116,32 @@ int chip_encode(uint8_t format, const uint8_t *pubkey, uint64_t pubkey_len, cons
 
 namespace {
 
+using hostbatch::HostGeo;
+
 // encode() at Zfec|Bao from host memory, split copy-back: the stream's data
-// region [0, t0) -- its header, the data-shard chunks [0, nd) and the parent
+// region [0, t0) -- its header, the data-shard chunks [0, nh) and the parent
 // nodes between them -- is half of the stream, and all of it but the nodes
-// is the zero-padded input the host already holds.  The host writes the
-// header and those chunks itself (host::fill_data_chunks, while it stages the
-// slice); the device gathers the region's nodes into a compact buffer
-// (bao_data_nodes); only that buffer and the tail [t0, final) cross PCIe,
-// and the host scatters the nodes into their slots once the slot's stream
-// is done.  D2H per 16 MiB object: 18.9 MB instead of 35.7.
-// CHIP_E2E_SPLIT=0: copy the whole stream back.
-struct SplitGeo {
-    uint64_t N = 0, nd = 0, t0 = 0, nb = 0;  // chunks, data chunks, data-region end, its nodes
-    std::vector<uint64_t> coff;              // [nd] stream offsets of the data chunks
-    struct Run {
-        uint64_t dst, src, len;  // stream offset, offset in the compact buffer, bytes
-    };
-    std::vector<Run> runs;
-    static SplitGeo make(uint64_t N) {
-        SplitGeo g;
-        g.N = N;
-        g.nd = N / 2;  // 4 of the 8 shards
-        g.coff.resize(g.nd);
-        uint64_t prev_end = 8, src = 0;
-        for (uint64_t i = 0; i < g.nd; ++i) {
-            g.coff[i] = bao_chunk_offset(i, N);
-            if (g.coff[i] > prev_end) {
-                g.runs.push_back({prev_end, src, g.coff[i] - prev_end});
-                src += g.coff[i] - prev_end;
-            }
-            prev_end = g.coff[i] + 1024;
-        }
-        g.t0 = prev_end;
-        g.nb = src / 64;
-        return g;
-    }
-};
+// is the zero-padded input the host already holds (hostbatch::HostGeo at
+// (1024 N, N / 2)).  The host writes the header and those chunks itself
+// (host::fill_data_chunks, while it stages the slice); the device gathers the
+// region's nodes into a compact buffer (bao_data_nodes); only that buffer and
+// the tail [t0, final) cross PCIe, and the host scatters the nodes into their
+// slots once the slot's stream is done.  D2H per 16 MiB object: 18.9 MB
+// instead of 35.7.  CHIP_E2E_SPLIT=0: copy the whole stream back.
+// CHIP_E2E_DIRECT=0: Ecies objects go through the pinned staging rows.
+// CHIP_ECIES_PREP=0: each object's scalar multiplications inside its host stage.
 
-// CHIP_E2E_DIRECT=0: Ecies objects go through the pinned staging rows
-bool direct_rows_on() {
-    static const bool on = [] {
-        const char *v = std::getenv("CHIP_E2E_DIRECT");
-        return !(v && v[0] == '0' && v[1] == 0);
-    }();
-    return on;
-}
-
-bool e2e_split_on() {
-    static const bool on = [] {
-        const char *v = std::getenv("CHIP_E2E_SPLIT");
-        return !(v && v[0] == '0' && v[1] == 0);
-    }();
-    return on;
-}
-
-// per-call cache of the geometry by chunk count (objects of a call may differ)
+// per-call cache of the split copy-back's geometry by chunk count (objects of a call may differ)
 struct SplitGeos {
     std::mutex mu;
-    std::map<uint64_t, SplitGeo> by_n;
-    const SplitGeo &get(uint64_t N) {
+    std::map<uint64_t, HostGeo> by_n;
+    const HostGeo &get(uint64_t N) {
         std::lock_guard<std::mutex> lk(mu);
         auto it = by_n.find(N);
-        if (it == by_n.end()) it = by_n.emplace(N, SplitGeo::make(N)).first;
+        if (it == by_n.end()) it = by_n.emplace(N, hostbatch::host_geo(1024 * N, N / 2, false)).first;
         return it->second;
     }
 };
-
-// chunk count of the bao stream of a Zfec|Bao object whose host stages left len bytes
-uint64_t split_chunks(uint64_t len) {
-    uint32_t pad;
-    uint64_t C;
-    calc_pad(len, CHIP_FEC_K, &pad, &C);
-    return (uint64_t)CHIP_FEC_M * C / 1024;
-}
-
-// fn(t) for t < nt on the caller and nt - 1 fresh threads.  (A persistent
-// team parked on a condition variable measured 30 % slower on the GPU box:
-// woken workers pile onto the waker's cores, r9p_session.)
-void run_threads(uint32_t nt, const std::function<void(uint32_t)> &fn) {
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < nt; ++t) pool.emplace_back(fn, t);
-    fn(0);
-    for (auto &th : pool) th.join();
-}
-
-// CHIP_ECIES_PREP=0: each object's scalar multiplications inside its host stage
-bool ecies_prep_on() {
-    static const bool on = [] {
-        const char *v = std::getenv("CHIP_ECIES_PREP");
-        return !(v && v[0] == '0' && v[1] == 0);
-    }();
-    return on;
-}
 
 // The ECIES key material of a slice's objects (host::ecies_prepare: two
 // scalar multiplications each, no data) computed on nt threads while the
@@ -270,25 +204,25 @@ struct CallTrace {
 
 // a slice waiting for its nodes: cnt objects, compact buffers at hnodes + j * nstride
 struct SplitPending {
-    const SplitGeo *g = nullptr;
+    const HostGeo *g = nullptr;
     uint8_t *out = nullptr;
     uint64_t pitch = 0, cnt = 0, nstride = 0;
     const uint8_t *hnodes = nullptr;
     void scatter(uint64_t j) const {
         const uint8_t *src = hnodes + j * nstride;
         uint8_t *dst = out + j * pitch;
-        for (const SplitGeo::Run &r : g->runs) std::memcpy(dst + r.dst, src + r.src, r.len);
+        for (const HostGeo::Run &r : g->runs) std::memcpy(dst + r.dst, src + r.src, r.len);
     }
 };
 
 // Device part of one slice of chip_encode_host_batch: cnt objects of cur_n
 // bytes at src (host, pitch src_pitch) -> zfec -> bao -> out (host).  With
 // split (Zfec|Bao only), the data region of every stream is the host's
-// (SplitGeo): the region's nodes go to sl.hnodes, the tail to out.
+// (HostGeo): the region's nodes go to sl.hnodes, the tail to out.
 int batch_slice_device(Slot &sl, uint8_t format, const GfPlan *plan, const chip_encode_info &inf,
                        const uint8_t *src, uint64_t src_pitch, uint64_t cur_n, uint64_t zlen, uint64_t final_len,
                        uint64_t cnt, uint8_t *out, uint64_t out_pitch, uint8_t *hashes, uint64_t stream_off,
-                       const SplitGeo *split = nullptr, bool from_rows = false) {
+                       const HostGeo *split = nullptr, bool from_rows = false) {
     const bool zfec = format & CHIP_FORMAT_ZFEC, bao = format & CHIP_FORMAT_BAO;
     // the streams 56 B into their rows: every chunk and node on a 64-B boundary
     // (K13, and K3 / the content mode for Bao alone; not KS, below 513 chunks)
@@ -315,9 +249,9 @@ int batch_slice_device(Slot &sl, uint8_t format, const GfPlan *plan, const chip_
                               sl.scratch.p, sl.stream));
         CHIP_HIP(hipMemcpyAsync(hashes, sl.hash.p, 32 * cnt, hipMemcpyDeviceToHost, sl.stream));
         if (split) {
-            const uint64_t ns = 64 * split->nb;
+            const uint64_t ns = split->nbytes;
             if (ns) {
-                CHIP_HIP(bao_data_nodes(d_str, f_al, split->N, split->nd, cnt, static_cast<uint8_t *>(sl.nodes.p), ns,
+                CHIP_HIP(bao_data_nodes(d_str, f_al, split->N, split->nh, cnt, static_cast<uint8_t *>(sl.nodes.p), ns,
                                         sl.stream));
                 CHIP_HIP(hipMemcpyAsync(sl.hnodes.p, sl.nodes.p, cnt * ns, hipMemcpyDeviceToHost, sl.stream));
             }
@@ -351,6 +285,276 @@ int batch_slice_device(Slot &sl, uint8_t format, const GfPlan *plan, const chip_
     return CHIP_OK;
 }
 
+struct EncodeArgs {  // of chip_encode_host_batch, checked
+    uint8_t format;
+    const uint8_t *pubkey; uint64_t pubkey_len; const chip_ecies_inject *inject;
+    const uint8_t *in; uint64_t n, count, in_stride;
+    uint8_t *out; uint64_t out_stride, *out_len; uint8_t *hashes; chip_encode_info *info;
+};
+
+// One chip_encode_host_batch call with a device or host stage: plan,
+// prepare_slots, then per slice wait_slot, host_slice, slice_infos and
+// device_slice, then finish.
+struct EncodeBatch : EncodeArgs {
+    hostbatch::EncodeBounds b;
+    const bool hs = has_host_stages(format), zfec = format & CHIP_FORMAT_ZFEC, bao = format & CHIP_FORMAT_BAO;
+    Ctx *c = nullptr;  // null: host stages only
+    hostbatch::Slices p{};
+    uint64_t h_al = 0;  // pinned staging pitch
+    // split copy-back (HostGeo): Zfec|Bao streams of at least 2 chunks; direct: with
+    // ECIES, the host stage writes each stream's data region straight into out
+    // (pinned), which the device then reads: no staging copy at all
+    bool split_fmt = false, direct_fmt = false;
+    // ECIES on the streaming path: the receiver key parsed once, each slice's
+    // key material prepared during its slot wait (KeyPrep)
+    bool prep = false;
+    uint64_t soff_cfg = 0;  // where K13's streams sit in the slot rows (this call)
+    SplitGeos geos;
+    std::vector<uint8_t> enc;           // the zfec encode matrix
+    std::vector<SplitPending> pend;     // per slot: the slice whose nodes are still to be placed
+    std::vector<uint8_t> stage_host;    // host stages without a device part
+    std::vector<Scratch> scratch;       // per host thread, reused across slices
+    std::vector<uint64_t> len, bc, be;  // per object of the slice: the host stages' output lengths
+    std::vector<uint64_t> zl, fl;       // ... and its zfec and final lengths
+    std::vector<chip_encode_info> infs;
+    std::vector<int> sts;
+    std::vector<uint8_t> in_rows;  // object's data region written straight into out (direct)
+    uint8_t peer[65];
+    KeyPrep kp;
+    CallTrace tr;
+    // the slice in hand
+    Slot *sl = nullptr;
+    uint64_t o0 = 0, cnt = 0;
+    const uint8_t *src = nullptr;  // what the device stages read: cnt objects of len[j] bytes
+    uint64_t src_pitch = 0;
+    bool uniform = true, rows = false;  // one length; all data regions already in out (direct)
+    // the geometry an incompressible object's stream will have: ECIES places
+    // its chunks block by block against it (host::ChunkSink)
+    uint64_t n_pred = 0;
+    const HostGeo *g_pred = nullptr;
+    bool direct = false;
+
+    const uint8_t *eph(uint64_t o) const {
+        return inject && inject->ephemeral_sk ? inject->ephemeral_sk + 32 * o : nullptr;
+    }
+    const uint8_t *nonce(uint64_t o) const { return inject && inject->nonce ? inject->nonce + 16 * o : nullptr; }
+    uint8_t *stage() { return sl ? static_cast<uint8_t *>(sl->stage.p) : stage_host.data(); }
+    SplitPending &pending() { return pend[(o0 / p.S) % p.nslots]; }  // this slot's previous slice
+
+    int plan(uint32_t nslots, uint64_t slice_bytes, uint32_t host_threads) {
+        if (zfec || bao) {
+            const int st = ctx_get(&c);
+            if (st != CHIP_OK) return st;
+        }
+        // host work per object (host stages, split copy-back): slices in equal shares
+        p = hostbatch::plan_slices(nslots, slice_bytes, host_threads, std::thread::hardware_concurrency(), b.h_max,
+                                   count, hs || (zfec && bao));
+        h_al = rules::up16(b.h_max);
+        static const bool split_on = env_default_on("CHIP_E2E_SPLIT"), direct_on = env_default_on("CHIP_E2E_DIRECT"),
+                          prep_on = env_default_on("CHIP_ECIES_PREP");
+        split_fmt = zfec && bao && c && split_on && b.zlen_max >= 2048;
+        direct_fmt = split_fmt && hs && stream_encrypt_on() && direct_on && out && host_pinned(out);
+        prep = (format & CHIP_FORMAT_ECIES) && stream_encrypt_on() && prep_on;
+        soff_cfg = stream_offset();
+        n_pred = split_fmt && hs ? hostbatch::split_chunks(b.h_max) : 0;
+        return CHIP_OK;
+    }
+
+    int prepare_slots() {
+        const uint64_t S = p.S, zmax = b.zlen_max;
+        if (c) {
+            if (c->slots.size() < p.nslots) c->slots.resize(p.nslots);
+            for (uint32_t k = 0; k < p.nslots; ++k) {
+                Slot &s = c->slots[k];
+                if (!s.stream) CHIP_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+                CHIP_HIP(grow(s.in, S * row_pitch(b.h_max)));
+                if (zfec && !bao) CHIP_HIP(grow(s.mid, S * row_pitch(zmax)));  // Zfec|Bao: fused
+                if (bao) {
+                    CHIP_HIP(grow(s.out, S * row_pitch(b.final_max + soff_cfg)));
+                    CHIP_HIP(grow(s.scratch, zfec ? std::max(zfec_bao_scratch_len(zmax, S), bao_scratch_len(zmax, S))
+                                                  : bao_scratch_len(zmax, S)));
+                }
+                CHIP_HIP(grow(s.hash, S * 32));
+                if (hs) CHIP_HIP(grow_pinned(s.stage, S * h_al));
+                if (split_fmt) {  // the data region's nodes: fewer than the stream's N chunks
+                    CHIP_HIP(grow(s.nodes, S * 64 * (zmax / 1024)));
+                    CHIP_HIP(grow_pinned(s.hnodes, S * 64 * (zmax / 1024)));
+                    if (direct_fmt) CHIP_HIP(grow(s.sin, S * row_pitch(geos.get(zmax / 1024).t0)));
+                }
+            }
+        } else {
+            stage_host.resize(S * h_al);
+        }
+        enc = zfec_enc_matrix(CHIP_FEC_K, CHIP_FEC_M);
+        pend.resize(p.nslots);
+        scratch.resize(p.T);
+        for (auto *v : {&len, &bc, &be, &zl, &fl}) v->resize(S);
+        infs.resize(S), sts.resize(S), in_rows.resize(S);
+        g_pred = n_pred >= 2 ? &geos.get(n_pred) : nullptr;
+        direct = direct_fmt && g_pred;
+        tr = CallTrace{};  // the clock starts with the slices
+        return prep ? host::ecies_peer(pubkey, pubkey_len, peer) : CHIP_OK;
+    }
+
+    // slice i in hand once its slot's previous slice is done; its ECIES key material meanwhile
+    int wait_slot(uint64_t i) {
+        sl = c ? &c->slots[i % p.nslots] : nullptr;
+        o0 = i * p.S, cnt = std::min(p.S, count - o0);
+        if (prep) kp.start(std::min<uint64_t>(p.T, cnt), peer, eph(o0), cnt);
+        const double t_a = tr.now();
+        const hipError_t e = sl && i >= p.nslots ? hipStreamSynchronize(sl->stream) : hipSuccess;
+        tr.wait += tr.now() - t_a;
+        if (prep) kp.finish();
+        if (e != hipSuccess) {
+            set_device_error(e);
+            return CHIP_ERR_DEVICE;
+        }
+        if (prep) tr.prep += tr.now() - t_a;
+        for (uint64_t j = 0; prep && j < cnt; ++j)
+            if (kp.sts[j] != CHIP_OK) return kp.sts[j];
+        return CHIP_OK;
+    }
+
+    // object j of the slice on a host thread: its host stages, then the header
+    // and data chunks of its stream (split copy-back)
+    void stage_object(uint64_t j, Scratch &tmp) {
+        const uint64_t o = o0 + j;
+        const uint8_t *obj = in + o * in_stride;
+        uint64_t olen = n, filled = 0;
+        uint8_t *row = out + o * out_stride;
+        in_rows[j] = 0;
+        if (hs) {
+            uint8_t *staged = stage() + j * h_al;
+            const host::ChunkSink sink{row, g_pred ? g_pred->coff.data() : nullptr, g_pred ? g_pred->nh : 0, direct,
+                                       1024 * n_pred};
+            sts[j] = host_stages_into(format, pubkey, pubkey_len, eph(o), nonce(o), obj, n, direct ? nullptr : staged,
+                                      h_al, tmp, &len[j], &bc[j], &be[j], g_pred ? &sink : nullptr, &filled,
+                                      prep ? &kp.keys[j] : nullptr);
+            if (sts[j] != CHIP_OK) return;
+            olen = len[j];
+            if (direct) {
+                if (hostbatch::split_chunks(olen) == n_pred) {  // the data region is complete in out
+                    host::fill_chunk_range(row, g_pred->coff.data(), filled, g_pred->nh, nullptr, 0);
+                    in_rows[j] = 1;
+                    return;
+                }
+                // another geometry (compressible input): the output back from the slots
+                host::gather_chunks(staged, row, g_pred->coff.data(), olen);
+                filled = 0;
+            }
+            obj = staged;
+        }
+        // the stream's header and data chunks (a ragged slice copies its
+        // streams back whole over this; chunks placed against a wrong
+        // prediction lie inside the stream and are overwritten too)
+        const uint64_t N = split_fmt ? hostbatch::split_chunks(olen) : 0;
+        if (N < 2) return;
+        const HostGeo &g = geos.get(N);
+        if (filled > 1 && N == n_pred) {  // chunks [1, filled) are in place
+            host::fill_data_chunks(row, g.coff.data(), 1, 1024 * N, obj, olen);
+            host::fill_chunk_range(row, g.coff.data(), filled, g.nh, obj, olen);
+        } else {
+            host::fill_data_chunks(row, g.coff.data(), g.nh, 1024 * N, obj, olen);
+        }
+    }
+
+    // On T threads while earlier slices run on the device: the nodes of this
+    // slot's previous slice into place, then this slice's host stages and the
+    // data region of its streams.  Leaves src / src_pitch / len[] / uniform / rows.
+    int host_slice() {
+        src = in + o0 * in_stride;
+        src_pitch = count > 1 ? in_stride : n;
+        uniform = true, rows = false;
+        for (uint64_t j = 0; j < cnt; ++j) len[j] = n, bc[j] = be[j] = 0;
+        if (!hs && !split_fmt) return CHIP_OK;
+        SplitPending &pp = pending();  // (its stream is done)
+        const uint32_t nt = (uint32_t)std::min<uint64_t>(p.T, std::max(cnt, pp.g ? pp.cnt : 0));
+        const double t_h = tr.now();
+        run_threads(nt, [&](uint32_t t) {
+            if (pp.g)
+                for (uint64_t j = t; j < pp.cnt; j += nt) pp.scatter(j);
+            for (uint64_t j = t; j < cnt; j += nt) stage_object(j, scratch[t]);
+        });
+        const double dh = tr.now() - t_h;
+        tr.host += dh;
+        tr.host_max = std::max(tr.host_max, dh);
+        pp = SplitPending{};
+        if (prep) kp.wipe();
+        if (!hs) return CHIP_OK;
+        for (uint64_t j = 0; j < cnt; ++j)
+            if (sts[j] != CHIP_OK) return sts[j];
+        src = stage();
+        src_pitch = h_al;
+        rows = direct;
+        for (uint64_t j = 0; j < cnt; ++j) uniform &= len[j] == len[0], rows &= in_rows[j] != 0;
+        rows &= uniform;
+        if (direct && !rows)  // a ragged slice: from the staging rows, as without `direct`
+            for (uint64_t j = 0; j < cnt; ++j)
+                if (in_rows[j])
+                    host::gather_chunks(stage() + j * h_al, out + (o0 + j) * out_stride, g_pred->coff.data(), len[j]);
+        return CHIP_OK;
+    }
+
+    // per-object EncodeInfo (identical for a uniform slice); zl / fl kept for the dispatch
+    int slice_infos() {
+        for (uint64_t j = 0; j < cnt; ++j) {
+            const int st = encode_info_for(format, n, len[j], bc[j], be[j], &infs[j], &zl[j], &fl[j]);
+            if (st != CHIP_OK) return st;
+            out_len[o0 + j] = fl[j];
+            if (info) info[o0 + j] = infs[j];
+        }
+        return CHIP_OK;
+    }
+
+    // the slice's device stages enqueued on its slot's stream: one batched pass
+    // over a uniform slice, one object at a time over a ragged one
+    // (compressible data through the host stages)
+    int device_slice() {
+        if (!sl) {  // host stages only (no Zfec/Bao bit)
+            for (uint64_t j = 0; j < cnt; ++j) {
+                std::memcpy(out + (o0 + j) * out_stride, src + j * src_pitch, len[j]);
+                std::memset(hashes + 32 * (o0 + j), 0, 32);
+            }
+            return CHIP_OK;
+        }
+        const uint64_t groups = uniform ? 1 : cnt, gcnt = uniform ? cnt : 1;
+        for (uint64_t j = 0; j < groups; ++j) {
+            const GfPlan gp = encode_plan(CHIP_FEC_K, CHIP_FEC_M, infs[j].chunk_len, enc);
+            const HostGeo *g = uniform && split_fmt && zl[j] >= 2048 ? &geos.get(zl[j] / 1024) : nullptr;
+            uint8_t *dst = out + (o0 + j) * out_stride;
+            const uint64_t opitch = uniform && count > 1 ? out_stride : fl[j];
+            const int st = batch_slice_device(*sl, format, &gp, infs[j], src + j * src_pitch, src_pitch, len[j], zl[j],
+                                              fl[j], gcnt, dst, opitch, hashes + 32 * (o0 + j), soff_cfg, g,
+                                              uniform && rows);
+            if (st != CHIP_OK) return st;
+            if (g) pending() = SplitPending{g, dst, opitch, cnt, g->nbytes, static_cast<const uint8_t *>(sl->hnodes.p)};
+        }
+        return CHIP_OK;
+    }
+
+    // the drain (the one error path's too), the trace report, the nodes of the last slices into place
+    int finish(int st) {
+        const double t_d = tr.now();
+        hipError_t e = hipSuccess;
+        for (uint32_t k = 0; c && k < p.nslots; ++k) {
+            const hipError_t ek = hipStreamSynchronize(c->slots[k].stream);
+            if (e == hipSuccess) e = ek;
+        }
+        if (st != CHIP_OK) return st;
+        CHIP_HIP(e);
+        tr.drain = tr.now() - t_d;
+        tr.report(p.nslices, p.S);
+        for (const SplitPending &pp : pend) {
+            if (!pp.g) continue;
+            const uint32_t nt = (uint32_t)std::min<uint64_t>(p.T, pp.cnt);
+            run_threads(nt, [&pp, nt](uint32_t t) {
+                for (uint64_t j = t; j < pp.cnt; j += nt) pp.scatter(j);
+            });
+        }
+        return CHIP_OK;
+    }
+};
+
 }  // namespace
 
 int chip_encode_host_batch(uint8_t format, const uint8_t *pubkey, uint64_t pubkey_len,
@@ -362,285 +566,34 @@ int chip_encode_host_batch(uint8_t format, const uint8_t *pubkey, uint64_t pubke
     if ((format & CHIP_FORMAT_ECIES) && !pubkey) return CHIP_ERR_INVALID_ARG;
     if (count > 1 && in_stride < n) return CHIP_ERR_INVALID_ARG;
     if (count == 0) return CHIP_OK;
-    const bool hs = has_host_stages(format);
-    const bool zfec = format & CHIP_FORMAT_ZFEC, bao = format & CHIP_FORMAT_BAO;
     // sizes: exact without host stages, bounds with them
-    const uint64_t h_max = hs ? host_stage_max(format, n) : n;
-    chip_encode_info inf_max;
-    uint64_t zlen_max, final_max;
-    int st = encode_info_for(format, n, h_max, 0, 0, &inf_max, &zlen_max, &final_max);
-    if (st != CHIP_OK && !hs) return st;
-    if (hs) {  // bound without the slice-count check (a smaller object may still pass it)
-        uint32_t pad;
-        uint64_t C;
-        calc_pad(h_max, CHIP_FEC_K, &pad, &C);
-        zlen_max = zfec ? (uint64_t)CHIP_FEC_M * C : h_max;
-        final_max = bao ? bao_encoded_len(zlen_max) : zlen_max;
-    }
-    if (count > 1 && out_stride < final_max) return CHIP_ERR_BUFFER_TOO_SMALL;
-    if (final_max && !out) return CHIP_ERR_BUFFER_TOO_SMALL;
-
-    if (!hs && !zfec && !bao) {  // format 0: identity, nothing for the device to do
+    const hostbatch::EncodeBounds b = hostbatch::encode_bounds(format, n);
+    if (b.st != CHIP_OK) return b.st;
+    if (count > 1 && out_stride < b.final_max) return CHIP_ERR_BUFFER_TOO_SMALL;
+    if (b.final_max && !out) return CHIP_ERR_BUFFER_TOO_SMALL;
+    if (!(format & (CHIP_FORMAT_ECIES | CHIP_FORMAT_SNAPPY | CHIP_FORMAT_ZFEC | CHIP_FORMAT_BAO))) {
+        // format 0: identity, nothing for the device to do
         for (uint64_t o = 0; o < count; ++o) {
             if (n) std::memcpy(out + o * out_stride, in + o * in_stride, n);
             std::memset(hashes + 32 * o, 0, 32);
             out_len[o] = n;
-            if (info) info[o] = inf_max;
+            if (info) info[o] = b.inf;
         }
         return CHIP_OK;
     }
-    Ctx *c = nullptr;
-    if (zfec || bao) {
-        st = ctx_get(&c);
-        if (st != CHIP_OK) return st;
+    EncodeBatch eb{{format, pubkey, pubkey_len, inject, in, n, count, in_stride, out, out_stride, out_len, hashes, info},
+                   b};
+    int st = eb.plan(nslots, slice_bytes, host_threads);
+    if (st != CHIP_OK) return st;
+    st = eb.prepare_slots();
+    if (st != CHIP_OK) return st;
+    for (uint64_t i = 0; i < eb.p.nslices && st == CHIP_OK; ++i) {
+        st = eb.wait_slot(i);
+        if (st == CHIP_OK) st = eb.host_slice();
+        if (st == CHIP_OK) st = eb.slice_infos();
+        if (st == CHIP_OK) st = eb.device_slice();
     }
-    nslots = nslots < 1 ? 3 : (nslots > 8 ? 8 : nslots);
-    if (slice_bytes == 0) slice_bytes = 256ull << 20;
-    uint32_t T = host_threads ? host_threads : std::max(1u, std::thread::hardware_concurrency());
-    T = std::min<uint32_t>(T, 64);
-    const uint64_t h_al = (h_max + 15) / 16 * 16;  // pinned staging pitch
-    uint64_t S = slice_bytes / (h_max ? h_max : 1);
-    S = S < 1 ? 1 : S;
-    // host work per object (host stages, split copy-back): a slice of at least half as
-    // many objects as host threads is rounded up to a multiple of them (equal shares)
-    if ((hs || (zfec && bao)) && S >= (T + 1) / 2) S = (S + T - 1) / T * T;
-    S = S > count ? count : S;
-    // split copy-back (SplitGeo): Zfec|Bao streams of at least 2 chunks
-    const bool split_fmt = zfec && bao && c && e2e_split_on() && zlen_max >= 2048;
-    // ...and with ECIES, the host stage writes each stream's data region straight
-    // into out (pinned), which the device then reads: no staging copy at all
-    const bool direct_fmt = split_fmt && hs && stream_encrypt_on() && direct_rows_on() && out && host_pinned(out);
-    SplitGeos geos;
-    const uint64_t soff_cfg = stream_offset();  // where K13's streams sit in the slot rows (this call)
-    if (c) {
-        if (c->slots.size() < nslots) c->slots.resize(nslots);
-        for (uint32_t k = 0; k < nslots; ++k) {
-            Slot &sl = c->slots[k];
-            if (!sl.stream) CHIP_HIP(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-            CHIP_HIP(grow(sl.in, S * row_pitch(h_max)));
-            if (zfec && !bao) CHIP_HIP(grow(sl.mid, S * row_pitch(zlen_max)));  // Zfec|Bao: fused
-            if (bao) {
-                CHIP_HIP(grow(sl.out, S * row_pitch(final_max + soff_cfg)));
-                CHIP_HIP(grow(sl.scratch, zfec ? std::max(zfec_bao_scratch_len(zlen_max, S), bao_scratch_len(zlen_max, S))
-                                                : bao_scratch_len(zlen_max, S)));
-            }
-            CHIP_HIP(grow(sl.hash, S * 32));
-            if (hs) CHIP_HIP(grow_pinned(sl.stage, S * h_al));
-            if (split_fmt) {  // the data region's nodes: fewer than the stream's N chunks
-                CHIP_HIP(grow(sl.nodes, S * 64 * (zlen_max / 1024)));
-                CHIP_HIP(grow_pinned(sl.hnodes, S * 64 * (zlen_max / 1024)));
-                if (direct_fmt) CHIP_HIP(grow(sl.sin, S * row_pitch(geos.get(zlen_max / 1024).t0)));
-            }
-        }
-    }
-    const std::vector<uint8_t> enc = zfec_enc_matrix(CHIP_FEC_K, CHIP_FEC_M);
-    std::vector<SplitPending> pend(nslots);  // per slot: the slice whose nodes are still to be placed
-    std::vector<uint8_t> stage_host;  // host stages without a device part
-    if (!c) stage_host.resize(S * h_al);
-    std::vector<uint64_t> len(S), bc(S), be(S);
-    std::vector<int> sts(S);
-    std::vector<uint8_t> in_rows(S);  // object's data region written straight into out (direct)
-    CallTrace tr;
-    std::vector<Scratch> scratch(T);  // per host thread, reused across slices
-    // ECIES on the streaming path: the receiver key parsed once, each slice's
-    // key material prepared during its slot wait (KeyPrep)
-    const bool prep = (format & CHIP_FORMAT_ECIES) && stream_encrypt_on() && ecies_prep_on();
-    uint8_t peer[65];
-    if (prep) {
-        st = host::ecies_peer(pubkey, pubkey_len, peer);
-        if (st != CHIP_OK) return st;
-    }
-    KeyPrep kp;
-    auto drain = [&]() {
-        if (c)
-            for (uint32_t k = 0; k < nslots; ++k) (void)hipStreamSynchronize(c->slots[k].stream);
-    };
-    const uint64_t nslices = (count + S - 1) / S;
-    for (uint64_t i = 0; i < nslices; ++i) {
-        Slot *sl = c ? &c->slots[i % nslots] : nullptr;
-        const uint64_t o0 = i * S, cnt = (count - o0) < S ? (count - o0) : S;
-        if (prep)
-            kp.start(std::min<uint64_t>(T, cnt), peer,
-                     inject && inject->ephemeral_sk ? inject->ephemeral_sk + 32 * o0 : nullptr, cnt);
-        const double t_a = tr.now();
-        if (sl && i >= nslots) {
-            const hipError_t e = hipStreamSynchronize(sl->stream);  // slot's previous slice is done
-            if (e != hipSuccess) {
-                kp.finish();
-                set_device_error(e);
-                return CHIP_ERR_DEVICE;
-            }
-        }
-        tr.wait += tr.now() - t_a;
-        if (prep) {
-            kp.finish();
-            tr.prep += tr.now() - t_a;
-            for (uint64_t j = 0; j < cnt; ++j)
-                if (kp.sts[j] != CHIP_OK) {
-                    drain();
-                    return kp.sts[j];
-                }
-        }
-        const uint8_t *src = in + o0 * in_stride;
-        uint64_t src_pitch = count > 1 ? in_stride : n;
-        uint64_t cur_n = n;
-        bool uniform = true, rows = false;
-        SplitPending &pp = pend[i % nslots];  // this slot's previous slice (its stream is done)
-        if (hs || split_fmt) {
-            // on T threads while earlier slices run on the device: the nodes of this
-            // slot's previous slice into place, then this slice's host stages and the
-            // data region of its streams (split copy-back)
-            uint8_t *stage = hs ? (sl ? static_cast<uint8_t *>(sl->stage.p) : stage_host.data()) : nullptr;
-            const uint32_t nt = (uint32_t)std::min<uint64_t>(T, std::max(cnt, pp.g ? pp.cnt : 0));
-            // the geometry an incompressible object's stream will have: ECIES places
-            // its chunks block by block against it (host::ChunkSink)
-            const uint64_t n_pred = split_fmt && hs ? split_chunks(h_max) : 0;
-            const SplitGeo *g_pred = n_pred >= 2 ? &geos.get(n_pred) : nullptr;
-            const bool direct = direct_fmt && g_pred;
-            auto work = [&](uint32_t t) {
-                Scratch &tmp = scratch[t];
-                if (pp.g)
-                    for (uint64_t j = t; j < pp.cnt; j += nt) pp.scatter(j);
-                for (uint64_t j = t; j < cnt; j += nt) {
-                    const uint64_t o = o0 + j;
-                    const uint8_t *obj = in + o * in_stride;
-                    uint64_t olen = n, filled = 0;
-                    uint8_t *row = out + o * out_stride;
-                    in_rows[j] = 0;
-                    if (hs) {
-                        const host::ChunkSink sink{row, g_pred ? g_pred->coff.data() : nullptr,
-                                                   g_pred ? g_pred->nd : 0, direct, 1024 * n_pred};
-                        sts[j] = host_stages_into(format, pubkey, pubkey_len,
-                                                  inject && inject->ephemeral_sk ? inject->ephemeral_sk + 32 * o
-                                                                                 : nullptr,
-                                                  inject && inject->nonce ? inject->nonce + 16 * o : nullptr, obj, n,
-                                                  direct ? nullptr : stage + j * h_al, h_al, tmp, &len[j], &bc[j],
-                                                  &be[j], g_pred ? &sink : nullptr, &filled,
-                                                  prep ? &kp.keys[j] : nullptr);
-                        if (sts[j] != CHIP_OK) continue;
-                        olen = len[j];
-                        if (direct) {
-                            if (split_chunks(olen) == n_pred) {  // the data region is complete in out
-                                host::fill_chunk_range(row, g_pred->coff.data(), filled, g_pred->nd, nullptr, 0);
-                                in_rows[j] = 1;
-                                continue;
-                            }
-                            // another geometry (compressible input): the output back from the slots
-                            host::gather_chunks(stage + j * h_al, row, g_pred->coff.data(), olen);
-                            filled = 0;
-                        }
-                        obj = stage + j * h_al;
-                    }
-                    // the stream's header and data chunks (a ragged slice copies its
-                    // streams back whole over this; chunks placed against a wrong
-                    // prediction lie inside the stream and are overwritten too)
-                    if (split_fmt) {
-                        const uint64_t N = split_chunks(olen);
-                        if (N >= 2) {
-                            const SplitGeo &g = geos.get(N);
-                            if (filled > 1 && N == n_pred) {  // chunks [1, filled) are in place
-                                host::fill_data_chunks(row, g.coff.data(), 1, 1024 * N, obj, olen);
-                                host::fill_chunk_range(row, g.coff.data(), filled, g.nd, obj, olen);
-                            } else {
-                                host::fill_data_chunks(row, g.coff.data(), g.nd, 1024 * N, obj, olen);
-                            }
-                        }
-                    }
-                }
-            };
-            const double t_h = tr.now();
-            run_threads(nt, work);
-            const double dh = tr.now() - t_h;
-            tr.host += dh;
-            tr.host_max = std::max(tr.host_max, dh);
-            pp = SplitPending{};
-            if (prep) kp.wipe();
-            if (hs) {
-                for (uint64_t j = 0; j < cnt; ++j)
-                    if (sts[j] != CHIP_OK) {
-                        drain();
-                        return sts[j];
-                    }
-                src = stage;
-                src_pitch = h_al;
-                cur_n = len[0];
-                for (uint64_t j = 1; j < cnt; ++j) uniform &= len[j] == cur_n;
-                rows = direct && uniform;
-                for (uint64_t j = 0; j < cnt; ++j) rows &= in_rows[j] != 0;
-                if (direct && !rows)  // a ragged slice: from the staging rows, as without `direct`
-                    for (uint64_t j = 0; j < cnt; ++j)
-                        if (in_rows[j])
-                            host::gather_chunks(stage + j * h_al, out + (o0 + j) * out_stride,
-                                                g_pred->coff.data(), len[j]);
-            }
-        }
-        if (!hs) {
-            for (uint64_t j = 0; j < cnt; ++j) len[j] = n, bc[j] = be[j] = 0;
-        }
-        // per-object EncodeInfo (identical for a uniform slice)
-        for (uint64_t j = 0; j < cnt; ++j) {
-            chip_encode_info inf;
-            uint64_t zl, fl;
-            st = encode_info_for(format, n, len[j], bc[j], be[j], &inf, &zl, &fl);
-            if (st != CHIP_OK) {
-                drain();
-                return st;
-            }
-            out_len[o0 + j] = fl;
-            if (info) info[o0 + j] = inf;
-        }
-        if (!sl) {  // host stages only (no Zfec/Bao bit)
-            for (uint64_t j = 0; j < cnt; ++j) {
-                std::memcpy(out + (o0 + j) * out_stride, src + j * src_pitch, len[j]);
-                std::memset(hashes + 32 * (o0 + j), 0, 32);
-            }
-            continue;
-        }
-        if (uniform) {
-            chip_encode_info inf;
-            uint64_t zl, fl;
-            (void)encode_info_for(format, n, cur_n, 0, 0, &inf, &zl, &fl);
-            const GfPlan p2 = encode_plan(CHIP_FEC_K, CHIP_FEC_M, inf.chunk_len, enc);
-            const SplitGeo *g = split_fmt && zl >= 2048 ? &geos.get(zl / 1024) : nullptr;
-            const uint64_t opitch = count > 1 ? out_stride : fl;
-            st = batch_slice_device(*sl, format, &p2, inf, src, src_pitch, cur_n, zl, fl, cnt, out + o0 * out_stride,
-                                    opitch, hashes + 32 * o0, soff_cfg, g, rows);
-            if (st != CHIP_OK) {
-                drain();
-                return st;
-            }
-            if (g)
-                pp = SplitPending{g, out + o0 * out_stride, opitch, cnt, 64 * g->nb,
-                                  static_cast<const uint8_t *>(sl->hnodes.p)};
-        } else {  // ragged host-stage output (compressible data): one object at a time
-            for (uint64_t j = 0; j < cnt; ++j) {
-                chip_encode_info inf;
-                uint64_t zl, fl;
-                (void)encode_info_for(format, n, len[j], 0, 0, &inf, &zl, &fl);
-                const GfPlan pj = encode_plan(CHIP_FEC_K, CHIP_FEC_M, inf.chunk_len, enc);
-                st = batch_slice_device(*sl, format, &pj, inf, src + j * src_pitch, src_pitch, len[j], zl, fl, 1,
-                                        out + (o0 + j) * out_stride, fl, hashes + 32 * (o0 + j), soff_cfg);
-                if (st != CHIP_OK) {
-                    drain();
-                    return st;
-                }
-            }
-        }
-    }
-    const double t_d = tr.now();
-    if (c)
-        for (uint32_t k = 0; k < nslots; ++k) CHIP_HIP(hipStreamSynchronize(c->slots[k].stream));
-    tr.drain = tr.now() - t_d;
-    tr.report(nslices, S);
-    // the nodes of the last slices into place
-    for (uint32_t k = 0; k < nslots; ++k) {
-        if (!pend[k].g) continue;
-        const uint32_t nt = (uint32_t)std::min<uint64_t>(T, pend[k].cnt);
-        run_threads(nt, [&pend, k, nt](uint32_t t) {
-            for (uint64_t j = t; j < pend[k].cnt; j += nt) pend[k].scatter(j);
-        });
-    }
-    return CHIP_OK;
+    return eb.finish(st);
 }
 
 }  // extern "C"

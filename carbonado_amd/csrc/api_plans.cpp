@@ -1,7 +1,9 @@
 // api_plans.cpp — zfec encode/decode plans, encode() at Zfec|Bao on the
-// device, bao and slice geometry, EncodeInfo, the host-stage glue, and the
-// device-side helpers several entry points share.  Shared declarations:
-// api_common.hpp.
+// device, bao and slice geometry, the host-stage glue, and the device-side
+// helpers several entry points share (EncodeInfo: hostbatch_plan.hpp).
+// Shared declarations: api_common.hpp.
+#include <thread>
+
 #include "api_common.hpp"
 
 namespace chip {
@@ -52,6 +54,11 @@ GfPlan encode_plan(uint32_t k, uint32_t m, uint64_t C, const std::vector<uint8_t
 int env_int(const char *name, int dflt) {
     const char *v = std::getenv(name);
     return v ? std::atoi(v) : dflt;
+}
+
+bool env_default_on(const char *name) {
+    const char *v = std::getenv(name);
+    return !(v && v[0] == '0' && v[1] == 0);
 }
 
 namespace {
@@ -260,58 +267,21 @@ void slice_nodes(uint64_t n, uint64_t c0, uint64_t c1, std::vector<SliceNode> *o
     }
 }
 
-// EncodeInfo of encode() for format bits Bao|Zfec (encoding.rs:86-172); no device
-// EncodeInfo of encode() (encoding.rs:86-171): `input_len` is the caller's
-// input, `cur` the length entering zfec (after snap/ecies), bc/be the
-// snap/ecies output lengths (0 when the stage is off, encoding.rs:101-115).
-int encode_info_for(uint8_t format, uint64_t input_len, uint64_t cur, uint64_t bc, uint64_t be,
-                    chip_encode_info *inf, uint64_t *zlen, uint64_t *final_len) {
-    std::memset(inf, 0, sizeof *inf);
-    inf->input_len = (uint32_t)input_len;  // encoding.rs:87 (as u32)
-    inf->bytes_compressed = (uint32_t)bc;
-    inf->bytes_encrypted = (uint32_t)be;
-    const bool zfec = format & CHIP_FORMAT_ZFEC, bao = format & CHIP_FORMAT_BAO;
-    uint64_t cur_len = cur;
-    if (zfec) {
-        uint32_t pad;
-        uint64_t C;
-        calc_pad(cur, CHIP_FEC_K, &pad, &C);
-        inf->padding_len = pad;
-        inf->chunk_len = (uint32_t)C;
-        cur_len = (uint64_t)CHIP_FEC_M * C;
-        inf->bytes_ecc = (uint32_t)cur_len;                                        // encoding.rs:123
-        inf->verifiable_slice_count = (uint16_t)(inf->bytes_ecc / CHIP_SLICE_LEN);  // encoding.rs:124
-        if (inf->verifiable_slice_count % 8 != 0) return CHIP_ERR_INVALID_VERIFIABLE_SLICE_COUNT;
-        inf->chunk_slice_count = inf->verifiable_slice_count / 8;                  // encoding.rs:130
-    }
-    const uint64_t fl = bao ? bao_encoded_len(cur_len) : cur_len;
-    if (bao) inf->bytes_verifiable = (uint32_t)fl;
-    inf->compression_factor = (float)inf->bytes_compressed / (float)inf->input_len;    // encoding.rs:150
-    inf->amplification_factor = (float)inf->bytes_verifiable / (float)inf->input_len;  // encoding.rs:151
-    inf->output_len = (uint32_t)fl;
-    *zlen = cur_len;
-    *final_len = fl;
-    return CHIP_OK;
-}
-
-bool has_host_stages(uint8_t format) { return format & (CHIP_FORMAT_ECIES | CHIP_FORMAT_SNAPPY); }
-
-
 // CHIP_STREAM_ENCRYPT=0: snap_compress into a full-size scratch, then
 // ecies_encrypt (the two-pass form, for A/B runs)
 bool stream_encrypt_on() {
-    static const bool on = [] {
-        const char *v = std::getenv("CHIP_STREAM_ENCRYPT");
-        return !(v && v[0] == '0' && v[1] == 0);
-    }();
+    static const bool on = env_default_on("CHIP_STREAM_ENCRYPT");
     return on;
 }
 
-// bound of the host stages' output for an n-byte input
-uint64_t host_stage_max(uint8_t format, uint64_t n) {
-    uint64_t m = (format & CHIP_FORMAT_SNAPPY) ? host::snap_max_len(n) : n;
-    if (format & CHIP_FORMAT_ECIES) m += host::ECIES_OVERHEAD;
-    return m;
+// fn(t) for t < nt on the caller and nt - 1 fresh threads.  (A persistent
+// team parked on a condition variable measured 30 % slower on the GPU box:
+// woken workers pile onto the waker's cores, r9p_session.)
+void run_threads(uint32_t nt, const std::function<void(uint32_t)> &fn) {
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < nt; ++t) pool.emplace_back(fn, t);
+    fn(0);
+    for (auto &th : pool) th.join();
 }
 
 // snap -> ecies (encoding.rs:101-115) of one object into dst[0..cap); tmp is
@@ -426,16 +396,6 @@ int bao_decode_ctx(Ctx *c, const uint8_t *d_enc, uint64_t len, uint64_t n, const
     CHIP_HIP(small_d2h(c, &status, d_status, 4));
     CHIP_HIP(small_sync(c));
     return status ? (int)status : CHIP_OK;
-}
-
-int bao_header(const uint8_t *enc, uint64_t len, uint64_t *n) {
-    if (len < 8) return CHIP_ERR_BAO_TRUNCATED;
-    uint64_t v = 0;
-    for (int i = 0; i < 8; ++i) v |= (uint64_t)enc[i] << (8 * i);
-    // a stream shorter than its header implies is truncated (also guards overflow)
-    if (v > len || bao_encoded_len(v) > len) return CHIP_ERR_BAO_TRUNCATED;
-    *n = v;
-    return CHIP_OK;
 }
 
 // node check of one host stream (already H2D'd to c->in); flags to host

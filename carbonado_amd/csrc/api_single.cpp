@@ -35,50 +35,16 @@ namespace api {
 
 namespace {
 
-// The host-made part of a stream of N chunks whose first `nh` chunks the host
-// holds: their slots, the parent-node runs between them (dst: stream offset,
-// src: offset in KM's compact node buffer) and the end t0 of that region.
-struct HostGeo {
-    uint64_t N = 0, nh = 0, zl = 0, t0 = 8, nbytes = 0;  // nbytes: compact node bytes
-    std::vector<uint64_t> coff;  // slots of chunks [0, nh), then (tail) of chunks [nh, N)
-    struct Run {
-        uint64_t dst, src, len;
-    };
-    std::vector<Run> runs;   // the nodes in front of t0: stream offset, compact offset, bytes
-    std::vector<Run> truns;  // the nodes past t0 (tail only): stream offset, -, bytes
-};
+using hostbatch::HostGeo;
 
+// the host-made part (hostbatch_plan.hpp) of the last few stream shapes of this thread
 const HostGeo &host_geo(uint64_t zl, uint64_t nh) {
     thread_local std::map<std::pair<uint64_t, uint64_t>, HostGeo> cache;
     auto key = std::make_pair(zl, nh);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
     if (cache.size() >= 8) cache.clear();
-    HostGeo g;
-    g.zl = zl;
-    g.N = n_chunks_of(zl);
-    g.nh = nh;
-    g.coff.resize(nh);
-    uint64_t prev_end = 8, src = 0;
-    for (uint64_t i = 0; i < nh; ++i) {
-        g.coff[i] = bao_chunk_offset(i, g.N);
-        if (g.coff[i] > prev_end) {
-            g.runs.push_back({prev_end, src, g.coff[i] - prev_end});
-            src += g.coff[i] - prev_end;
-        }
-        prev_end = g.coff[i] + std::min<uint64_t>(1024, zl - 1024 * i);
-    }
-    g.t0 = prev_end;
-    g.nbytes = src;
-    if (nh < g.N) {  // the tail: chunk slots and the node runs between them
-        g.coff.resize(g.N);
-        for (uint64_t i = nh; i < g.N; ++i) {
-            g.coff[i] = bao_chunk_offset(i, g.N);
-            if (g.coff[i] > prev_end) g.truns.push_back({prev_end, 0, g.coff[i] - prev_end});
-            prev_end = g.coff[i] + std::min<uint64_t>(1024, zl - 1024 * i);
-        }
-    }
-    return cache.emplace(key, std::move(g)).first->second;
+    return cache.emplace(key, hostbatch::host_geo(zl, nh)).first->second;
 }
 
 // host copy threads for `bytes`: one per 128 KiB, at most CHIP_ZC_THREADS

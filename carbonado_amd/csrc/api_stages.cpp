@@ -68,10 +68,8 @@ int chip_zfec_encode_batch_dev(uint32_t k, uint32_t m, const uint8_t *d_in, uint
     if (aliased && (uint64_t)k * C > n)  // the zero padding of encoding.rs:53-55 becomes part of shard k-1
         CHIP_HIP(hipMemset2DAsync(d_out + n, out_stride ? out_stride : (uint64_t)m * C, 0, (uint64_t)k * C - n,
                                   count, s));
-    CHIP_HIP(zf_run(count, s, [&](uint64_t o0, uint64_t cnt, hipStream_t st) {
-        GfLaunch L{d_in + o0 * in_stride, d_out + o0 * out_stride, in_stride, out_stride, n, C, cnt};
-        return gf_apply(p, L, st);
-    }));
+    GfLaunch L{d_in, d_out, in_stride, out_stride, n, C, count};
+    CHIP_HIP(gf_apply(p, L, s));
     return CHIP_OK;
 }
 
@@ -88,11 +86,9 @@ int chip_hbm_pattern_batch_dev(uint32_t k, uint32_t m, const uint8_t *d_in, uint
     calc_pad(n, k, &pad, &C);
     if (count > 1 && (out_stride < (uint64_t)m * C || in_stride < n)) return CHIP_ERR_INVALID_ARG;
     GfPlan p = encode_plan(k, m, C, zfec_enc_matrix(k, m), false);
-    CHIP_HIP(zf_run(count, static_cast<hipStream_t>(stream), [&](uint64_t o0, uint64_t cnt, hipStream_t s) {
-        GfLaunch L{d_in + o0 * in_stride, d_out + o0 * out_stride, in_stride, out_stride, n, C, cnt};
-        L.pattern_only = true;
-        return gf_apply(p, L, s);
-    }));
+    GfLaunch L{d_in, d_out, in_stride, out_stride, n, C, count};
+    L.pattern_only = true;
+    CHIP_HIP(gf_apply(p, L, static_cast<hipStream_t>(stream)));
     return CHIP_OK;
 }
 
@@ -203,17 +199,8 @@ int chip_zfec_decode_batch_dev(uint32_t k, uint32_t m, const uint8_t *d_in, uint
     }
     // rows would overlap
     if (count > 1 && (in_stride < row_in || out_stride < (uint64_t)k * chunk_len)) return CHIP_ERR_INVALID_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int part_st = CHIP_OK;
-    const hipError_t e = zf_run(count, s, [&](uint64_t o0, uint64_t cnt, hipStream_t st) {
-        const int r = zfec_decode_device(k, m, d_in + o0 * in_stride, in_stride, slot_off, sel, chunk_len, cnt,
-                                         d_out + o0 * out_stride, out_stride, st);
-        if (r != CHIP_OK) part_st = r;
-        return r == CHIP_OK ? hipSuccess : hipErrorInvalidValue;
-    });
-    if (part_st != CHIP_OK) return part_st;
-    CHIP_HIP(e);
-    return CHIP_OK;
+    return zfec_decode_device(k, m, d_in, in_stride, slot_off, sel, chunk_len, count, d_out, out_stride,
+                              static_cast<hipStream_t>(stream));
 }
 
 

@@ -174,7 +174,7 @@ def test_encode_host_batch_stream_offset(gpu, level, n, soff, monkeypatch):
 def test_encode_host_batch_split_copy_back(gpu, level, n):
     """Zfec|Bao from host memory: the host writes each stream's header and
     data-shard chunks itself, the device gathers the parent nodes between them
-    and the tail crosses PCIe (api_encode.cpp SplitGeo).  Output pre-filled with
+    and the tail crosses PCIe (hostbatch_plan.hpp HostGeo).  Output pre-filled with
     0xA5 so a byte nobody wrote shows; nine objects over two slots of two
     objects each, so slots are reused and nodes scattered while the next slice
     stages; count 1 separately (pitch = the stream length)."""
@@ -348,6 +348,33 @@ def test_decode_host_batch_roundtrip(gpu, level):
         assert st[2] == 5 and st[:2] == [0, 0] and st[3:] == [0] * (count - 3)
         for o in (0, 1, 3):
             assert out[o, :n].numpy().tobytes() == rows[o].tobytes()
+
+
+def test_decode_host_batch_geometry_error_inside_a_slice(gpu):
+    """Five level-12 objects over two slots of two: object 1's length is three
+    bytes short of its stream (a host-side geometry error, so its slice goes
+    object by object around it), object 3 has a content byte flipped (the
+    device's verdict inside a batched slice).  Each fails alone, with the status
+    the CPU check pins for that header and bao's mismatch."""
+    import torch
+    from carbonado_amd import device
+    from test_hostbatch_cpu import HEADER_SHORT_STATUS
+    n, count = 10_000, 5
+    rng = np.random.default_rng(12)
+    inp = torch.from_numpy(rng.integers(0, 256, (count, n), dtype=np.uint8))
+    enc = torch.zeros((count, device._lib.lib().chip_encode_max_len(n)), dtype=torch.uint8)
+    hashes = torch.zeros((count, 32), dtype=torch.uint8)
+    olen, info = device.encode_host_batch(12, inp, n, enc, hashes)
+    assert len(set(olen)) == 1
+    in_len = list(olen)
+    in_len[1] -= 3
+    enc[3, olen[3] // 2] ^= 1
+    out = torch.zeros((count, n + 64), dtype=torch.uint8)
+    dlen, st = device.decode_host_batch(12, enc, in_len, hashes, [i.padding_len for i in info], out, nslots=2,
+                                        slice_bytes=2 * olen[0], host_threads=3, raise_first=False)
+    assert st == [0, HEADER_SHORT_STATUS, 0, 5, 0] and HEADER_SHORT_STATUS != 0
+    for o in (0, 2, 4):
+        assert dlen[o] == n and out[o, :n].numpy().tobytes() == inp[o].numpy().tobytes(), o
 
 
 @pytest.mark.parametrize("n", [0, 1, 4096, 12_288, 70_001, (1 << 20) + 1, 3 << 20])
