@@ -32,6 +32,7 @@ mod ffi_cread;
 mod ffi_fread;
 mod ffi_qread;
 mod ffi_kread;
+mod ffi_gread;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -2160,6 +2161,95 @@ pub fn read_plain_ranges_planned(table: &DeviceBuffer, info: &TableInfo, key_tab
     abi_kread()?;
     check(unsafe {
         ffi_kread::chipk_read_ranges_dev(table.ptr, info, key_table.ptr, key_table.len() as u64,
+                                         req_stream.as_ptr() as *const u32, start.as_ptr() as *const u64,
+                                         len.as_ptr() as *const u64, nreq, max_len, content.as_mut_ptr(),
+                                         content_stride, content_len.as_mut_ptr() as *mut u64,
+                                         status.as_mut_ptr() as *mut u32, used.as_mut_ptr() as *mut u32,
+                                         vouch.as_mut_ptr() as *mut u32, flags, scratch.ptr, scratch.len() as u64,
+                                         stream.0)
+    })
+}
+
+fn abi_gread() -> Result<()> {
+    abi_kread()?;
+    abi_fread()?;
+    match unsafe { ffi_gread::chipg_abi_version() } {
+        ffi_gread::CHIPG_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// What the planned reads know of a frame table: the number of streams, the
+/// index entries it holds, the longest frame among them and the format (14 or
+/// 15).
+pub type FrameInfo = ffi_gread::chipg_frame_info;
+
+/// Bytes of device memory the frame table of `nstreams` streams with
+/// `nentries` index entries in all needs ([`frame_table`]).
+pub fn frame_table_len(nstreams: u64, nentries: u64) -> u64 {
+    unsafe { ffi_gread::chipg_frame_table_len(nstreams, nentries) }
+}
+
+/// Describe the frame indexes of resident level-14 / level-15 streams once
+/// (the index arguments of [`read_frame_ranges`], as [`frame_index`] or
+/// [`verify_frame_index`] proved them) in `table`, for every later
+/// [`read_frame_ranges_planned`] call: the checks that call makes of every
+/// index on every call, made once, and the one upload, enqueued on `stream`.
+/// The table stays valid while the streams are not re-encoded.
+#[allow(clippy::too_many_arguments)]
+pub fn frame_table(format: u8, chunk_len: &[u32], padding: &[u32], index_status: Option<&[u32]>, frame_off: &[u64],
+                   idx_off: &[u64], nframes: &[u64], plain_len: &[u64], table: &mut DeviceBuffer, stream: Stream)
+                   -> Result<FrameInfo> {
+    let count = chunk_len.len();
+    if padding.len() != count || idx_off.len() != count || nframes.len() != count || plain_len.len() != count ||
+        index_status.map_or(false, |k| k.len() != count) ||
+        idx_off.iter().zip(nframes).any(|(&o, &n)| {
+            o.checked_add(n).and_then(|e| e.checked_add(1)).map_or(true, |e| e > frame_off.len() as u64)
+        }) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_gread()?;
+    let mut info = FrameInfo::default();
+    check(unsafe {
+        ffi_gread::chipg_frame_table_dev(format, chunk_len.as_ptr(), padding.as_ptr(),
+                                         index_status.map_or(ptr::null(), |k| k.as_ptr()), frame_off.as_ptr(),
+                                         idx_off.as_ptr(), nframes.as_ptr(), plain_len.as_ptr(), count as u64,
+                                         table.ptr, table.len() as u64, &mut info, stream.0)
+    })?;
+    Ok(info)
+}
+
+/// Scratch of a [`read_frame_ranges_planned`] call of capacity (`nreq`,
+/// `max_len`); 0 where the call would refuse it.
+pub fn planned_frame_read_scratch_len(info: &TableInfo, finfo: &FrameInfo, nreq: u64, max_len: u64) -> u64 {
+    unsafe { ffi_gread::chipg_read_scratch_len(info, finfo, nreq, max_len) }
+}
+
+/// [`read_frame_ranges`] for requests that live on the device: the arguments
+/// of [`read_ranges_vouched_planned`] with requests in PLAINTEXT bytes of
+/// level-14 / level-15 streams, over the stream table, the frame table
+/// ([`frame_table`]) and, at 15, the key table ([`key_table`]; `None` at 14)
+/// of the same streams.  A request the device refuses has status 1; a request
+/// on a stream whose index status or key status is not 0 has that status,
+/// zeros over its clipped range, used 0 and vouch 0.  Kernel launches only;
+/// enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn read_frame_ranges_planned(table: &DeviceBuffer, info: &TableInfo, frame_table: &DeviceBuffer,
+                                 finfo: &FrameInfo, key_table: Option<&DeviceBuffer>, req_stream: &DeviceBuffer,
+                                 start: &DeviceBuffer, len: &DeviceBuffer, nreq: u64, max_len: u64,
+                                 content: &mut DeviceBuffer, content_stride: u64, content_len: &mut DeviceBuffer,
+                                 status: &mut DeviceBuffer, used: &mut DeviceBuffer, vouch: &mut DeviceBuffer,
+                                 flags: u32, scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    if !planned_fits(nreq, max_len, req_stream, start, len, content, content_stride, content_len,
+                     &[status, used, vouch]) ||
+        (frame_table.len() as u64) < frame_table_len(finfo.nstreams, finfo.nentries) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_gread()?;
+    check(unsafe {
+        ffi_gread::chipg_read_ranges_dev(table.ptr, info, frame_table.ptr, finfo,
+                                         key_table.map_or(ptr::null(), |k| k.ptr as *const _),
+                                         key_table.map_or(0, |k| k.len() as u64),
                                          req_stream.as_ptr() as *const u32, start.as_ptr() as *const u64,
                                          len.as_ptr() as *const u64, nreq, max_len, content.as_mut_ptr(),
                                          content_stride, content_len.as_mut_ptr() as *mut u64,

@@ -403,6 +403,31 @@ KREAD_SIGNATURES = {
                                              ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
 }
 
+
+# the gread header (include/carbonado_hip_gread.h): plaintext ranged reads of
+# level-14 / level-15 streams planned on the device over a resident frame
+# table, a thirteenth table of its own
+class FrameInfo(ctypes.Structure):
+    """chipg_frame_info: what the planned reads know of a frame table."""
+    _fields_ = [("nstreams", ctypes.c_uint64), ("nentries", ctypes.c_uint64), ("max_frame", ctypes.c_uint64),
+                ("format", ctypes.c_uint64)]
+
+
+c_finfop = ctypes.POINTER(FrameInfo)
+GREAD_SIGNATURES = {
+    "chipg_abi_version": (ctypes.c_int, []),
+    "chipg_frame_table_len": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "chipg_frame_table_dev": (ctypes.c_int, [ctypes.c_uint8, c_u32p, c_u32p, c_u32p, c_u64p, c_u64p, c_u64p, c_u64p,
+                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, c_finfop,
+                                             ctypes.c_void_p]),
+    "chipg_read_scratch_len": (ctypes.c_uint64, [c_infop, c_finfop, ctypes.c_uint64, ctypes.c_uint64]),
+    "chipg_read_ranges_dev": (ctypes.c_int, [ctypes.c_void_p, c_infop, ctypes.c_void_p, c_finfop, ctypes.c_void_p,
+                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -426,7 +451,7 @@ def lib() -> ctypes.CDLL:
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES,
                                   **READ_SIGNATURES, **VREAD_SIGNATURES, **ECIES_SIGNATURES,
                                   **SNAP_SIGNATURES, **CREAD_SIGNATURES, **FREAD_SIGNATURES,
-                                  **QREAD_SIGNATURES, **KREAD_SIGNATURES}.items():
+                                  **QREAD_SIGNATURES, **KREAD_SIGNATURES, **GREAD_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

@@ -6,14 +6,76 @@
 // work (kread::plan_call) and enqueues KK's rewrite, the device-planned vouched
 // read of api_qread.cpp over the rewritten requests, and KK's keystream
 // kernel.  Kernels only: no upload, no memset, no synchronisation, no
-// allocation after the thread's first call.
-#include "api_qread.hpp"
+// allocation after the thread's first call.  The read's enqueue is
+// read_plain_planned, declared in api_kread.hpp: api_gread.cpp runs it over
+// requests its own kernel rewrote.
+#include "api_kread.hpp"
 #include "cread_kernels.hpp"
 #include "key_upload.hpp"
-#include "kread_kernels.hpp"
 
 using namespace chip;
 using namespace chip::api;
+
+namespace chip {
+namespace api {
+
+int read_plain_planned(const KreadCall &a) {
+    const void *d_table = a.q.d_table;
+    const chipq_table_info *info = a.q.info;
+    const void *d_keytab = a.d_keytab;
+    const uint64_t keytab_len = a.keytab_len;
+    const uint32_t *d_req_stream = a.q.d_req_stream;
+    const uint64_t *d_start = a.q.d_start, *d_len = a.q.d_len;
+    const uint64_t nreq = a.q.nreq, max_len = a.q.max_len, content_stride = a.q.content_stride;
+    uint8_t *d_content = a.q.d_content;
+    uint64_t *d_content_len = a.q.d_content_len;
+    uint32_t *d_status = a.q.d_status, *d_used = a.q.d_used, *d_vouch = a.q.d_vouch;
+    const uint32_t flags = a.q.flags;
+    void *d_scratch = a.q.d_scratch;
+    const uint64_t scratch_len = a.q.scratch_len;
+    void *stream = a.q.stream;
+    if (nreq == 0) return CHIP_OK;
+    kread::Geometry g;
+    kread::ScratchLayout lay;
+    int st = kread::plan_call(reinterpret_cast<uintptr_t>(d_table), info, reinterpret_cast<uintptr_t>(d_keytab),
+                              keytab_len, d_req_stream && d_start && d_len, nreq, max_len,
+                              reinterpret_cast<uintptr_t>(d_content), content_stride,
+                              d_content_len && d_status && d_used && d_vouch, flags,
+                              reinterpret_cast<uintptr_t>(d_scratch), scratch_len, &g, &lay);
+    if (st != CHIP_OK) return st;
+    st = use_device();
+    if (st != CHIP_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t *scr = static_cast<uint8_t *>(d_scratch);
+    const uint8_t *tab = static_cast<const uint8_t *>(d_keytab);
+    const kread::TableLayout tl(info->nstreams);
+
+    KreadLaunch K{};
+    K.recs = reinterpret_cast<const qread::StreamRec *>(d_table);
+    K.shape = qread::Shape{info->nstreams, info->max_chunks, info->min_shard, max_len, g.q.S};
+    K.km = reinterpret_cast<const cread::CtrKey *>(tab + tl.km);
+    K.key_status = reinterpret_cast<const uint32_t *>(tab + tl.status);
+    K.req_stream = d_req_stream; K.start = d_start; K.len = d_len;
+    K.q_stream = reinterpret_cast<uint32_t *>(scr + lay.q_stream);
+    K.q_start = reinterpret_cast<uint64_t *>(scr + lay.q_start);
+    K.q_len = reinterpret_cast<uint64_t *>(scr + lay.q_len);
+    K.nreq = uint32_t(nreq); K.cap = g.cap;
+    K.content = d_content; K.stride = content_stride;
+    K.content_len = d_content_len;
+    K.status = d_status; K.used = d_used; K.vouch = d_vouch;
+    CHIP_HIP(kread_rewrite_launch(K, s));
+    // the vouched read of the envelope requests, in the front part of the scratch
+    st = read_planned(QreadCall{d_table, info, K.q_stream, K.q_start, K.q_len, nreq, max_len, d_content,
+                                content_stride, d_content_len, d_status, d_used, d_vouch, flags, d_scratch,
+                                lay.q.total, stream},
+                      true);
+    if (st != CHIP_OK) return st;
+    CHIP_HIP(kread_ctr_launch(K, s));
+    return CHIP_OK;
+}
+
+}  // namespace api
+}  // namespace chip
 
 extern "C" {
 
@@ -65,44 +127,10 @@ int chipk_read_ranges_dev(const void *d_table, const chipq_table_info *info, con
                           uint64_t max_len, uint8_t *d_content, uint64_t content_stride, uint64_t *d_content_len,
                           uint32_t *d_status, uint32_t *d_used, uint32_t *d_vouch, uint32_t flags, void *d_scratch,
                           uint64_t scratch_len, void *stream) {
-    if (nreq == 0) return CHIP_OK;
-    kread::Geometry g;
-    kread::ScratchLayout lay;
-    int st = kread::plan_call(reinterpret_cast<uintptr_t>(d_table), info, reinterpret_cast<uintptr_t>(d_keytab),
-                              keytab_len, d_req_stream && d_start && d_len, nreq, max_len,
-                              reinterpret_cast<uintptr_t>(d_content), content_stride,
-                              d_content_len && d_status && d_used && d_vouch, flags,
-                              reinterpret_cast<uintptr_t>(d_scratch), scratch_len, &g, &lay);
-    if (st != CHIP_OK) return st;
-    st = use_device();
-    if (st != CHIP_OK) return st;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint8_t *scr = static_cast<uint8_t *>(d_scratch);
-    const uint8_t *tab = static_cast<const uint8_t *>(d_keytab);
-    const kread::TableLayout tl(info->nstreams);
-
-    KreadLaunch K{};
-    K.recs = reinterpret_cast<const qread::StreamRec *>(d_table);
-    K.shape = qread::Shape{info->nstreams, info->max_chunks, info->min_shard, max_len, g.q.S};
-    K.km = reinterpret_cast<const cread::CtrKey *>(tab + tl.km);
-    K.key_status = reinterpret_cast<const uint32_t *>(tab + tl.status);
-    K.req_stream = d_req_stream; K.start = d_start; K.len = d_len;
-    K.q_stream = reinterpret_cast<uint32_t *>(scr + lay.q_stream);
-    K.q_start = reinterpret_cast<uint64_t *>(scr + lay.q_start);
-    K.q_len = reinterpret_cast<uint64_t *>(scr + lay.q_len);
-    K.nreq = uint32_t(nreq); K.cap = g.cap;
-    K.content = d_content; K.stride = content_stride;
-    K.content_len = d_content_len;
-    K.status = d_status; K.used = d_used; K.vouch = d_vouch;
-    CHIP_HIP(kread_rewrite_launch(K, s));
-    // the vouched read of the envelope requests, in the front part of the scratch
-    st = read_planned(QreadCall{d_table, info, K.q_stream, K.q_start, K.q_len, nreq, max_len, d_content,
-                                content_stride, d_content_len, d_status, d_used, d_vouch, flags, d_scratch,
-                                lay.q.total, stream},
-                      true);
-    if (st != CHIP_OK) return st;
-    CHIP_HIP(kread_ctr_launch(K, s));
-    return CHIP_OK;
+    return read_plain_planned(KreadCall{QreadCall{d_table, info, d_req_stream, d_start, d_len, nreq, max_len, d_content,
+                                                  content_stride, d_content_len, d_status, d_used, d_vouch, flags,
+                                                  d_scratch, scratch_len, stream},
+                                        d_keytab, keytab_len});
 }
 
 }  // extern "C"

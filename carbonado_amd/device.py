@@ -1246,6 +1246,87 @@ def read_frame_ranges(fmt: int, streams: torch.Tensor, in_off, in_len, hashes: t
     return clen.tolist()
 
 
+# ---- plaintext reads of level-14 / level-15 streams planned on the device
+# (include/carbonado_hip_gread.h): the frame indexes are checked and uploaded
+# once into a resident table, the requests are device tensors, nothing is
+# uploaded per call
+
+class FrameTable:
+    """The resident frame indexes of a set of level-14 / level-15 streams
+    (frame_table): the device table and what the planned reads know of it on
+    the host."""
+
+    def __init__(self, table: torch.Tensor, info: "_lib.FrameInfo"):
+        self.table, self.info = table, info
+
+    nstreams = property(lambda self: self.info.nstreams)
+    nentries = property(lambda self: self.info.nentries)
+    max_frame = property(lambda self: self.info.max_frame)
+    format = property(lambda self: self.info.format)
+
+
+def frame_table(fmt: int, chunk_len, padding, frame_off, idx_off, nframes, plain_len, index_status=None,
+                device=None) -> FrameTable:
+    """Describe the frame indexes of resident streams once (the index arguments
+    of read_frame_ranges, as frame_index or verify_frame_index proved them):
+    the checks read_frame_ranges makes on every call, one record per stream and
+    the entries of the streams whose index_status is 0, uploaded on the current
+    stream.  The table serves every later read_frame_ranges_planned call while
+    the streams are not re-encoded."""
+    (fo, (io, nf, pl, cl, pad)), (pfo, (pio, pnf, ppl, pcl, ppad)), nstreams = _index_args(
+        frame_off, idx_off, nframes, plain_len, chunk_len, padding, kinds="QII")
+    ist, pis = _opt(index_status, nstreams)
+    size = _lib.lib().chipg_frame_table_len(nstreams, int(nf.sum()) + nstreams)
+    if nstreams and not size:
+        raise ValueError("too many streams or index entries for one frame table")
+    table = torch.empty(size, dtype=torch.uint8, device=device or "cuda")
+    info = _lib.FrameInfo()
+    check(_lib.lib().chipg_frame_table_dev(fmt, pcl, ppad, pis, pfo, pio, pnf, ppl, nstreams, _p(table), table.numel(),
+                                           ctypes.byref(info), _stream()))
+    return FrameTable(table, info)
+
+
+def planned_frame_read_scratch(table: StreamTable, frames: FrameTable, nreq: int, max_len: int,
+                               device=None) -> torch.Tensor:
+    """Scratch of a read_frame_ranges_planned call of capacity (nreq, max_len)
+    over `table` and `frames`: the inner planned read's scratch and one staging
+    slot per request for the compressed frames a range of max_len bytes can
+    touch."""
+    size = _lib.lib().chipg_read_scratch_len(ctypes.byref(table.info), ctypes.byref(frames.info), nreq, max_len)
+    if nreq and not size:
+        raise ValueError("the call would refuse this capacity")
+    return _scratch(size, device or table.table.device)
+
+
+def read_frame_ranges_planned(table: StreamTable, frames: FrameTable, key_table, req_stream: torch.Tensor,
+                              start: torch.Tensor, length: torch.Tensor, max_len: int, content: torch.Tensor,
+                              content_stride: int, content_len: torch.Tensor, status: torch.Tensor,
+                              used: torch.Tensor, vouch: torch.Tensor, scratch: torch.Tensor, flags: int = 0) -> None:
+    """read_frame_ranges for requests that live on the device: the arguments of
+    read_ranges_vouched_planned with requests in PLAINTEXT bytes of level-14 /
+    level-15 streams, over the stream table, the frame table and, at 15, a key
+    table of the same streams (key_table: None at 14).  status: 1 for a request
+    the device refuses (as read_ranges_planned; a frame record that contradicts
+    the frame table's info), the stream's index_status or, at 15, key_status
+    where that is not 0 (zeros over the clipped range, used 0, vouch 0), else
+    read_frame_ranges' status, words and bytes.  Kernel launches only: after one
+    warm-up call the call can be captured into a graph and replayed with the
+    request tensors rewritten in place.  Enqueued on the current stream."""
+    nreq = _planned_args(table, req_stream, start, length, max_len, content, content_stride, content_len,
+                         (status, used, vouch), scratch)
+    assert frames.table.is_cuda and frames.table.is_contiguous()
+    ktab, klen = None, 0
+    if frames.format == 15:
+        assert key_table is not None and key_table.table.is_cuda and key_table.table.is_contiguous()
+        assert key_table.nstreams == table.nstreams
+        ktab, klen = _p(key_table.table), key_table.table.numel()
+    check(_lib.lib().chipg_read_ranges_dev(_p(table.table), ctypes.byref(table.info), _p(frames.table),
+                                           ctypes.byref(frames.info), ktab, klen, _p(req_stream), _p(start),
+                                           _p(length), nreq, max_len, _p(content), content_stride, _p(content_len),
+                                           _p(status), _p(used), _p(vouch), flags, _p(scratch), scratch.numel(),
+                                           _stream()))
+
+
 def host_topology() -> dict:
     """Where this process's host-copy path sits (chip_host_topology): the
     GPU's NUMA node, the calling thread's staging ring node and the copy
