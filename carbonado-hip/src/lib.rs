@@ -33,6 +33,7 @@ mod ffi_fread;
 mod ffi_qread;
 mod ffi_kread;
 mod ffi_gread;
+mod ffi_paudit;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -2256,6 +2257,145 @@ pub fn read_frame_ranges_planned(table: &DeviceBuffer, info: &TableInfo, frame_t
                                          status.as_mut_ptr() as *mut u32, used.as_mut_ptr() as *mut u32,
                                          vouch.as_mut_ptr() as *mut u32, flags, scratch.ptr, scratch.len() as u64,
                                          stream.0)
+    })
+}
+
+fn abi_paudit() -> Result<()> {
+    abi_qread()?;
+    match unsafe { ffi_paudit::chipp_abi_version() } {
+        ffi_paudit::CHIPP_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// What [`verify_slice_proofs_planned`] knows of a root table: the number of
+/// audited streams and the largest chunk count among them.
+pub type RootInfo = ffi_paudit::chipp_root_info;
+
+/// `req_stream` of a spare slot of a planned audit.
+pub const NO_REQUEST: u32 = ffi_paudit::CHIPP_NO_REQUEST;
+
+/// Bytes of device memory the root table of `nroots` audited streams needs ([`root_table`]).
+pub fn root_table_len(nroots: u64) -> u64 {
+    unsafe { ffi_paudit::chipp_root_table_len(nroots) }
+}
+
+/// The auditor's one upload: stream s has `content_len[s]` content bytes and
+/// its expected root is `hashes[32 s..]` (device, stays where it is).
+/// Enqueued on `stream`.
+pub fn root_table(content_len: &[u64], hashes: &DeviceBuffer, table: &mut DeviceBuffer, stream: Stream)
+                  -> Result<RootInfo> {
+    let count = content_len.len();
+    if hashes.len() < count * HASH_LEN || (table.len() as u64) < root_table_len(count as u64) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_paudit()?;
+    let mut info = RootInfo::default();
+    check(unsafe {
+        ffi_paudit::chipp_root_table_dev(content_len.as_ptr(), hashes.as_ptr(), count as u64, table.ptr,
+                                         table.len() as u64, &mut info, stream.0)
+    })?;
+    Ok(info)
+}
+
+/// Scratch of a planned audit of capacity (`nreq`, `max_count`) over a table
+/// whose largest chunk count is `max_chunks`; 0 where the call would refuse it.
+pub fn planned_audit_scratch_len(max_chunks: u64, nreq: u64, max_count: u64) -> u64 {
+    unsafe { ffi_paudit::chipp_audit_scratch_len(max_chunks, nreq, max_count) }
+}
+
+/// The most bytes a proof of `max_count` chunks of a stream of `max_chunks` chunks can have.
+pub fn proof_bound(max_chunks: u64, max_count: u64) -> u64 {
+    unsafe { ffi_paudit::chipp_proof_bound(max_chunks, max_count) }
+}
+
+fn slots_fit(nreq: u64, stride: u64, least: u64, buf: &DeviceBuffer) -> bool {
+    nreq == 0 || (nreq - 1).checked_mul(stride).and_then(|x| x.checked_add(least.min(stride)))
+        .map_or(false, |e| e <= buf.len() as u64)
+}
+
+fn audit_requests_fit(nreq: u64, req_stream: &DeviceBuffer, index: &DeviceBuffer, count: &DeviceBuffer,
+                      lens: &[&DeviceBuffer], status: &DeviceBuffer) -> bool {
+    let n = nreq as usize;
+    req_stream.len() >= n * 4 && index.len() >= n * 8 && count.len() >= n * 8 && status.len() >= n * 4 &&
+        lens.iter().all(|l| l.len() >= n * 8)
+}
+
+/// [`verify_slices`] for requests that live on the device: `req_stream` (u32;
+/// [`NO_REQUEST`]: a spare slot), `index` and `count` (u64) are device arrays
+/// of `nreq` entries, read by the GPU only; `nreq` and `max_count` (selected
+/// chunks per request) are the capacity of the call.  Request r's content goes
+/// to `content[r * content_stride..]`, its length to `content_len[r]` (u64, on
+/// the device).  A request the device refuses has status 1.  Kernel launches
+/// only; enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn verify_slices_planned(table: &DeviceBuffer, info: &TableInfo, req_stream: &DeviceBuffer, index: &DeviceBuffer,
+                             count: &DeviceBuffer, nreq: u64, max_count: u64, content: &mut DeviceBuffer,
+                             content_stride: u64, content_len: &mut DeviceBuffer, status: &mut DeviceBuffer,
+                             scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    if !audit_requests_fit(nreq, req_stream, index, count, &[content_len], status) ||
+        !slots_fit(nreq, content_stride, max_count.saturating_mul(1024), content) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_paudit()?;
+    check(unsafe {
+        ffi_paudit::chipp_verify_slices_dev(table.ptr, info, req_stream.as_ptr() as *const u32,
+                                            index.as_ptr() as *const u64, count.as_ptr() as *const u64, nreq,
+                                            max_count, content.as_mut_ptr(), content_stride,
+                                            content_len.as_mut_ptr() as *mut u64, status.as_mut_ptr() as *mut u32,
+                                            scratch.ptr, scratch.len() as u64, stream.0)
+    })
+}
+
+/// [`extract_slices`] for requests that live on the device (as
+/// [`verify_slices_planned`]): request r's proof goes to
+/// `proofs[r * proof_stride..]`, its exact length to `proof_len[r]` (u64, on
+/// the device); `proof_stride` is at least [`proof_bound`].  Status 0, or 1
+/// for a request the device refuses.
+#[allow(clippy::too_many_arguments)]
+pub fn extract_slices_planned(table: &DeviceBuffer, info: &TableInfo, req_stream: &DeviceBuffer, index: &DeviceBuffer,
+                              count: &DeviceBuffer, nreq: u64, max_count: u64, proofs: &mut DeviceBuffer,
+                              proof_stride: u64, proof_len: &mut DeviceBuffer, status: &mut DeviceBuffer,
+                              scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    if !audit_requests_fit(nreq, req_stream, index, count, &[proof_len], status) ||
+        !slots_fit(nreq, proof_stride, proof_bound(info.max_chunks, max_count), proofs) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_paudit()?;
+    check(unsafe {
+        ffi_paudit::chipp_extract_slices_dev(table.ptr, info, req_stream.as_ptr() as *const u32,
+                                             index.as_ptr() as *const u64, count.as_ptr() as *const u64, nreq,
+                                             max_count, proofs.as_mut_ptr(), proof_stride,
+                                             proof_len.as_mut_ptr() as *mut u64, status.as_mut_ptr() as *mut u32,
+                                             scratch.ptr, scratch.len() as u64, stream.0)
+    })
+}
+
+/// The auditor's side for requests and proofs that live on the device:
+/// `req_stream[r]` names the audited stream of the root table whose proof
+/// sits in `proofs[r * proof_stride..]`, `proof_len[r]` (u64, on the device,
+/// read) the bytes that arrived.  Status 6 where that is not the proof's exact
+/// length (content zeros), else as [`verify_slices_planned`].
+#[allow(clippy::too_many_arguments)]
+pub fn verify_slice_proofs_planned(roots: &DeviceBuffer, root_info: &RootInfo, req_stream: &DeviceBuffer,
+                                   index: &DeviceBuffer, count: &DeviceBuffer, nreq: u64, max_count: u64,
+                                   proofs: &DeviceBuffer, proof_stride: u64, proof_len: &DeviceBuffer,
+                                   content: &mut DeviceBuffer, content_stride: u64, content_len: &mut DeviceBuffer,
+                                   status: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream)
+                                   -> Result<()> {
+    if !audit_requests_fit(nreq, req_stream, index, count, &[proof_len, content_len], status) ||
+        !slots_fit(nreq, proof_stride, proof_bound(root_info.max_chunks, max_count), proofs) ||
+        !slots_fit(nreq, content_stride, max_count.saturating_mul(1024), content) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_paudit()?;
+    check(unsafe {
+        ffi_paudit::chipp_verify_proofs_dev(roots.ptr, root_info, req_stream.as_ptr() as *const u32,
+                                            index.as_ptr() as *const u64, count.as_ptr() as *const u64, nreq,
+                                            max_count, proofs.as_ptr(), proof_stride,
+                                            proof_len.as_ptr() as *const u64, content.as_mut_ptr(), content_stride,
+                                            content_len.as_mut_ptr() as *mut u64, status.as_mut_ptr() as *mut u32,
+                                            scratch.ptr, scratch.len() as u64, stream.0)
     })
 }
 

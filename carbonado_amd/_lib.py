@@ -428,6 +428,38 @@ GREAD_SIGNATURES = {
                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
 }
 
+
+# the paudit header (include/carbonado_hip_paudit.h): slice audits planned on
+# the device from requests (and proofs) in device memory, a fourteenth table of
+# its own
+class RootInfo(ctypes.Structure):
+    """chipp_root_info: what the planned proof check knows of a root table."""
+    _fields_ = [("nroots", ctypes.c_uint64), ("max_chunks", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 2)]
+
+
+c_rinfop = ctypes.POINTER(RootInfo)
+PAUDIT_SIGNATURES = {
+    "chipp_abi_version": (ctypes.c_int, []),
+    "chipp_root_table_len": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "chipp_root_table_dev": (ctypes.c_int, [c_u64p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                            c_rinfop, ctypes.c_void_p]),
+    "chipp_audit_scratch_len": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]),
+    "chipp_proof_bound": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "chipp_verify_slices_dev": (ctypes.c_int, [ctypes.c_void_p, c_infop, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                               ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_uint64, ctypes.c_void_p]),
+    "chipp_extract_slices_dev": (ctypes.c_int, [ctypes.c_void_p, c_infop, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.c_void_p]),
+    "chipp_verify_proofs_dev": (ctypes.c_int, [ctypes.c_void_p, c_rinfop, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                               ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -451,7 +483,8 @@ def lib() -> ctypes.CDLL:
         for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **AUDIT_SIGNATURES, **REPAIR_SIGNATURES,
                                   **READ_SIGNATURES, **VREAD_SIGNATURES, **ECIES_SIGNATURES,
                                   **SNAP_SIGNATURES, **CREAD_SIGNATURES, **FREAD_SIGNATURES,
-                                  **QREAD_SIGNATURES, **KREAD_SIGNATURES, **GREAD_SIGNATURES}.items():
+                                  **QREAD_SIGNATURES, **KREAD_SIGNATURES, **GREAD_SIGNATURES,
+                                  **PAUDIT_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

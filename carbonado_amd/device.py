@@ -674,6 +674,124 @@ def read_ranges_vouched_planned(table: StreamTable, req_stream: torch.Tensor, st
                                                    _p(scratch), scratch.numel(), _stream()))
 
 
+# ---- slice audits planned on the device (include/carbonado_hip_paudit.h): the
+# requests (and, for the auditor, the proofs) are device tensors, a kernel plans
+# them, nothing is uploaded per call.  The holder's calls take the StreamTable
+# of stream_table, the auditor's a RootTable
+
+NO_REQUEST = 0xFFFFFFFF  # req_stream of a spare slot (CHIPP_NO_REQUEST)
+
+
+class RootTable:
+    """The auditor's resident description of the streams it audits
+    (root_table): the device table and what the planned check knows of it."""
+
+    def __init__(self, table: torch.Tensor, info: "_lib.RootInfo"):
+        self.table, self.info = table, info
+
+    nroots = property(lambda self: self.info.nroots)
+    max_chunks = property(lambda self: self.info.max_chunks)
+
+
+def root_table(content_lens, hashes: torch.Tensor) -> RootTable:
+    """Describe audited streams once: content_lens[s] content bytes (host) and
+    hashes uint8 [nroots, 32] on the device, which must stay where they are.
+    Uploaded on the current stream."""
+    (n,), (pn,), nroots = _cols("Q", content_lens)
+    _hashes(hashes, nroots)
+    table = torch.empty(max(_lib.lib().chipp_root_table_len(nroots), 16), dtype=torch.uint8, device=hashes.device)
+    info = _lib.RootInfo()
+    check(_lib.lib().chipp_root_table_dev(pn, _p(hashes), nroots, _p(table), table.numel(), ctypes.byref(info),
+                                          _stream()))
+    return RootTable(table, info)
+
+
+def proof_bound(max_chunks: int, max_count: int) -> int:
+    """The most bytes a proof of max_count chunks of a stream of max_chunks chunks can have."""
+    return _lib.lib().chipp_proof_bound(max_chunks, max_count)
+
+
+def planned_audit_scratch(table, nreq: int, max_count: int, device=None) -> torch.Tensor:
+    """Scratch of a verify_slices_planned / extract_slices_planned /
+    verify_slice_proofs_planned call of capacity (nreq, max_count) over `table`
+    (a StreamTable or a RootTable)."""
+    size = _lib.lib().chipp_audit_scratch_len(table.max_chunks, nreq, max_count)
+    if nreq and not size:
+        raise ValueError("the call would refuse this capacity")
+    return _scratch(size, device or table.table.device)
+
+
+def _planned_audit_args(table, req_stream, index, count, slots, lens, status, scratch):
+    """The checks of a planned audit's tensors; slots = [(buffer, stride, min bytes of a slot)]."""
+    nreq = req_stream.numel()
+    assert index.numel() == count.numel() == nreq
+    assert req_stream.element_size() == 4 and index.element_size() == count.element_size() == 8
+    for t in (req_stream, index, count, scratch, table.table, *lens):
+        assert t.is_cuda and t.is_contiguous()
+    for t in lens:
+        assert t.numel() >= nreq and t.element_size() == 8
+    _words(nreq, status)
+    for buf, stride, least in slots:
+        _flat(buf)
+        assert nreq == 0 or buf.numel() >= (nreq - 1) * stride + min(stride, least)
+    return nreq
+
+
+def verify_slices_planned(table: StreamTable, req_stream: torch.Tensor, index: torch.Tensor, count: torch.Tensor,
+                          max_count: int, content: torch.Tensor, content_stride: int, content_len: torch.Tensor,
+                          status: torch.Tensor, scratch: torch.Tensor) -> None:
+    """verify_slices for requests that live on the device: req_stream (int32 /
+    uint32; NO_REQUEST: a spare slot), index and count (int64 / uint64) are
+    device tensors of nreq entries, read by the GPU only; nreq and max_count
+    (selected chunks per request) are the capacity of the call.  Request r's
+    content goes to content[r * content_stride :], its length to content_len[r]
+    (device int64 / uint64).  status: 1 for a request the device refuses
+    (stream index, index or count above 2^53, more than max_count chunks), else
+    verify_slices' status and bytes.  The host work is O(1) and nothing is
+    uploaded: after one warm-up call the call can be captured into a graph and
+    replayed with the request tensors rewritten in place.  Enqueued on the
+    current stream."""
+    nreq = _planned_audit_args(table, req_stream, index, count, [(content, content_stride, 1024 * max_count)],
+                               [content_len], status, scratch)
+    check(_lib.lib().chipp_verify_slices_dev(_p(table.table), ctypes.byref(table.info), _p(req_stream), _p(index),
+                                             _p(count), nreq, max_count, _p(content), content_stride, _p(content_len),
+                                             _p(status), _p(scratch), scratch.numel(), _stream()))
+
+
+def extract_slices_planned(table: StreamTable, req_stream: torch.Tensor, index: torch.Tensor, count: torch.Tensor,
+                           max_count: int, proofs: torch.Tensor, proof_stride: int, proof_len: torch.Tensor,
+                           status: torch.Tensor, scratch: torch.Tensor) -> None:
+    """extract_slices for requests that live on the device (as
+    verify_slices_planned): request r's proof goes to proofs[r * proof_stride :],
+    its exact length to proof_len[r]; proof_stride is at least
+    proof_bound(table.max_chunks, max_count).  status: 0, or 1 for a request the
+    device refuses."""
+    nreq = _planned_audit_args(table, req_stream, index, count,
+                               [(proofs, proof_stride, proof_bound(table.max_chunks, max_count))], [proof_len], status,
+                               scratch)
+    check(_lib.lib().chipp_extract_slices_dev(_p(table.table), ctypes.byref(table.info), _p(req_stream), _p(index),
+                                              _p(count), nreq, max_count, _p(proofs), proof_stride, _p(proof_len),
+                                              _p(status), _p(scratch), scratch.numel(), _stream()))
+
+
+def verify_slice_proofs_planned(roots: RootTable, req_stream: torch.Tensor, index: torch.Tensor, count: torch.Tensor,
+                                max_count: int, proofs: torch.Tensor, proof_stride: int, proof_len: torch.Tensor,
+                                content: torch.Tensor, content_stride: int, content_len: torch.Tensor,
+                                status: torch.Tensor, scratch: torch.Tensor) -> None:
+    """The auditor's side for requests and proofs that live on the device:
+    req_stream[r] names the audited stream of `roots` whose proof sits in
+    proofs[r * proof_stride :], proof_len[r] (device, read) the bytes that
+    arrived.  status: 6 where proof_len[r] is not the proof's exact length
+    (content zeros), else as verify_slices_planned."""
+    nreq = _planned_audit_args(roots, req_stream, index, count,
+                               [(proofs, proof_stride, proof_bound(roots.max_chunks, max_count)),
+                                (content, content_stride, 1024 * max_count)], [proof_len, content_len], status, scratch)
+    check(_lib.lib().chipp_verify_proofs_dev(_p(roots.table), ctypes.byref(roots.info), _p(req_stream), _p(index),
+                                             _p(count), nreq, max_count, _p(proofs), proof_stride, _p(proof_len),
+                                             _p(content), content_stride, _p(content_len), _p(status), _p(scratch),
+                                             scratch.numel(), _stream()))
+
+
 # ---- AES-256-GCM over resident messages (include/carbonado_hip_ecies.h): the
 # data half of the Ecies stage, one ragged batch per call
 
