@@ -34,6 +34,7 @@ mod ffi_qread;
 mod ffi_kread;
 mod ffi_gread;
 mod ffi_paudit;
+mod ffi_agree;
 
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -2396,6 +2397,207 @@ pub fn verify_slice_proofs_planned(roots: &DeviceBuffer, root_info: &RootInfo, r
                                             proof_len.as_ptr() as *const u64, content.as_mut_ptr(), content_stride,
                                             content_len.as_mut_ptr() as *mut u64, status.as_mut_ptr() as *mut u32,
                                             scratch.ptr, scratch.len() as u64, stream.0)
+    })
+}
+
+fn abi_agree() -> Result<()> {
+    abi_ecies()?;
+    match unsafe { ffi_agree::chipy_abi_version() } {
+        ffi_agree::CHIPY_ABI_VERSION => Ok(()),
+        v => Err(ChipError::AbiMismatch(v)),
+    }
+}
+
+/// Scratch of a [`seal_keys`] / [`open_keys`] call over `count` objects.
+pub fn agree_scratch_len(count: u64) -> u64 {
+    unsafe { ffi_agree::chipy_keys_scratch_len(count) }
+}
+
+/// Scratch of [`ecies_seal_ragged_dev_keys`] / [`ecies_open_ragged_dev_keys`] over plaintexts of `n[o]` bytes.
+pub fn envelope_scratch_len(n: &[u64]) -> u64 {
+    unsafe { ffi_agree::chipy_envelope_scratch_len(n.as_ptr(), n.len() as u64) }
+}
+
+fn pitched(buf_len: usize, pitch: u64, width: u64, count: u64) -> bool {
+    count == 0 || (pitch >= width && (count - 1).checked_mul(pitch).and_then(|x| x.checked_add(width))
+        .map_or(false, |e| e <= buf_len as u64))
+}
+
+/// The Ecies key agreement of a seal on the device, per object o: the
+/// ephemeral public key k_o G (0x04 || x || y) to `pubs[o * pub_pitch..][..65]`
+/// and the AES key HKDF(E65 || (k_o P)65) to `keys[o * key_pitch..][..32]`, P
+/// the receiver `pubkey` (33 or 65 bytes).  `eph_sk`: 32 bytes per object, or
+/// `None` for secrets from the library's RNG.  secp256k1 and HKDF-SHA256 run
+/// as kernels, constant time in the scalars; the AES keys stay in `keys`, which
+/// the caller wipes.  Enqueued on `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn seal_keys(pubkey: &[u8], eph_sk: Option<&[u8]>, count: u64, pubs: &mut DeviceBuffer, pub_pitch: u64,
+                 keys: &mut DeviceBuffer, key_pitch: u64, scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    if eph_sk.map_or(false, |s| s.len() as u64 != 32 * count) || !pitched(pubs.len(), pub_pitch, 65, count) ||
+        !pitched(keys.len(), key_pitch, 32, count) || (scratch.len() as u64) < agree_scratch_len(count) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_agree()?;
+    check(unsafe {
+        ffi_agree::chipy_seal_keys_dev(pubkey.as_ptr(), pubkey.len() as u64, eph_sk.map_or(ptr::null(), |s| s.as_ptr()),
+                                       count, pubs.as_mut_ptr(), pub_pitch, keys.as_mut_ptr(), key_pitch, scratch.ptr,
+                                       scratch.len() as u64, stream.0)
+    })
+}
+
+/// The key agreement of an open on the device, per object o: the AES key
+/// HKDF(R65 || (sk R)65) of the ephemeral key R = `eph[o * eph_pitch..][..65]`
+/// to `keys[o * key_pitch..][..32]` and `status[o]` = 0 (u32 per object, on
+/// the device); or [`ECIES_FAILED`] and a key of zeros for an R that does not
+/// parse.  The AES keys stay in `keys`, which the caller wipes.  Enqueued on
+/// `stream`, not synchronised.
+#[allow(clippy::too_many_arguments)]
+pub fn open_keys(secret_key: &[u8], eph: &DeviceBuffer, eph_pitch: u64, count: u64, keys: &mut DeviceBuffer,
+                 key_pitch: u64, status: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    if !pitched(eph.len(), eph_pitch, 65, count) || !pitched(keys.len(), key_pitch, 32, count) ||
+        (status.len() as u64) < 4 * count || (scratch.len() as u64) < agree_scratch_len(count) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_agree()?;
+    check(unsafe {
+        ffi_agree::chipy_open_keys_dev(secret_key.as_ptr(), secret_key.len() as u64, eph.as_ptr(), eph_pitch, count,
+                                       keys.as_mut_ptr(), key_pitch, status.as_mut_ptr() as *mut u32, scratch.ptr,
+                                       scratch.len() as u64, stream.0)
+    })
+}
+
+/// [`ecies_seal_ragged`] with the key agreement on the device: no host
+/// elliptic-curve work.  `scratch` holds [`envelope_scratch_len`]`(n)` bytes.
+#[allow(clippy::too_many_arguments)]
+pub fn ecies_seal_ragged_dev_keys(pubkey: &[u8], input: &DeviceBuffer, in_off: &[u64], n: &[u64],
+                                  out: &mut DeviceBuffer, out_off: &[u64], scratch: &mut DeviceBuffer, stream: Stream)
+                                  -> Result<()> {
+    let count = n.len();
+    let need = envelope_scratch_len(n);
+    if in_off.len() != count || out_off.len() != count || !ranges_fit(in_off, n, 0, input.len()) ||
+        !ranges_fit(out_off, n, 97, out.len()) || (count > 0 && need == 0) || (scratch.len() as u64) < need {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_agree()?;
+    check(unsafe {
+        ffi_agree::chipy_seal_ragged_dev(pubkey.as_ptr(), pubkey.len() as u64, ptr::null(), input.as_ptr(),
+                                         in_off.as_ptr(), n.as_ptr(), count as u64, out.as_mut_ptr(), out_off.as_ptr(),
+                                         scratch.ptr, stream.0)
+    })
+}
+
+/// [`ecies_open_ragged`] with the key agreement on the device: no copy back
+/// and no wait.  `scratch` holds [`envelope_scratch_len`] of the plaintext
+/// lengths.  Returns the plaintext length per object.
+#[allow(clippy::too_many_arguments)]
+pub fn ecies_open_ragged_dev_keys(secret_key: &[u8], input: &DeviceBuffer, in_off: &[u64], in_len: &[u64],
+                                  out: &mut DeviceBuffer, out_off: &[u64], status: &mut DeviceBuffer,
+                                  scratch: &mut DeviceBuffer, stream: Stream) -> Result<Vec<u64>> {
+    let count = in_len.len();
+    let plain: Vec<u64> = in_len.iter().map(|&l| l.saturating_sub(97)).collect();
+    let need = envelope_scratch_len(&plain);
+    if in_off.len() != count || out_off.len() != count || status.len() < 4 * count ||
+        !ranges_fit(in_off, in_len, 0, input.len()) || !ranges_fit(out_off, &plain, 0, out.len()) ||
+        (count > 0 && need == 0) || (scratch.len() as u64) < need {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_agree()?;
+    let mut olen = vec![0u64; count];
+    check(unsafe {
+        ffi_agree::chipy_open_ragged_dev(secret_key.as_ptr(), secret_key.len() as u64, input.as_ptr(), in_off.as_ptr(),
+                                         in_len.as_ptr(), count as u64, out.as_mut_ptr(), out_off.as_ptr(),
+                                         olen.as_mut_ptr(), status.as_mut_ptr() as *mut u32, scratch.ptr, stream.0)
+    })?;
+    Ok(olen)
+}
+
+/// Scratch of [`encode_ragged_ecies_dev_keys`] (object lengths) / [`decode_ragged_ecies_dev_keys`] (stream lengths).
+pub fn ecies_ragged_scratch_len_dev_keys(format: u8, lens: &[u64], decode: bool) -> u64 {
+    unsafe {
+        if decode {
+            ffi_agree::chipy_decode_scratch_len(format, lens.as_ptr(), lens.len() as u64)
+        } else {
+            ffi_agree::chipy_encode_scratch_len(format, lens.as_ptr(), lens.len() as u64)
+        }
+    }
+}
+
+/// [`encode_ragged_ecies`] with the key agreement on the device.
+#[allow(clippy::too_many_arguments)]
+pub fn encode_ragged_ecies_dev_keys(format: u8, pubkey: &[u8], input: &DeviceBuffer, in_off: &[u64], sizes: &[u64],
+                                    out: &mut DeviceBuffer, out_off: &[u64], hashes: &mut DeviceBuffer,
+                                    scratch: &mut DeviceBuffer, stream: Stream)
+                                    -> Result<(Vec<u64>, Vec<ChipEncodeInfo>)> {
+    let count = sizes.len();
+    let env: Vec<u64> = sizes.iter().map(|&n| n + 97).collect();
+    let need_scratch = ecies_ragged_scratch_len_dev_keys(format, sizes, false);
+    if in_off.len() != count || out_off.len() != count || hashes.len() < count * HASH_LEN || need_scratch == 0 ||
+        (scratch.len() as u64) < need_scratch || !ranges_fit(in_off, sizes, 0, input.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    let (_, need, _) = ragged_layout(format & 12, &env, 256, 0)?;
+    if !ranges_fit(out_off, &need, 0, out.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_agree()?;
+    let mut lens = vec![0u64; count];
+    let mut infos = vec![ChipEncodeInfo::default(); count];
+    check(unsafe {
+        ffi_agree::chipy_encode_ragged_dev(format, pubkey.as_ptr(), pubkey.len() as u64, ptr::null(), input.as_ptr(),
+                                           in_off.as_ptr(), sizes.as_ptr(), count as u64, out.as_mut_ptr(),
+                                           out_off.as_ptr(), lens.as_mut_ptr(), hashes.as_mut_ptr(), infos.as_mut_ptr(),
+                                           scratch.ptr, stream.0)
+    })?;
+    Ok((lens, infos))
+}
+
+/// [`decode_ragged_ecies`] with the key agreement on the device: the call no
+/// longer blocks.  Returns the plaintext lengths.
+#[allow(clippy::too_many_arguments)]
+pub fn decode_ragged_ecies_dev_keys(format: u8, secret_key: &[u8], input: &DeviceBuffer, in_off: &[u64],
+                                    in_len: &[u64], hashes: &DeviceBuffer, padding: &[u32], out: &mut DeviceBuffer,
+                                    out_off: &[u64], status: &mut DeviceBuffer, scratch: &mut DeviceBuffer,
+                                    stream: Stream) -> Result<Vec<u64>> {
+    let count = in_len.len();
+    let need_scratch = ecies_ragged_scratch_len_dev_keys(format, in_len, true);
+    if in_off.len() != count || out_off.len() != count || padding.len() != count || hashes.len() < count * HASH_LEN ||
+        status.len() < 4 * count || need_scratch == 0 || (scratch.len() as u64) < need_scratch ||
+        !ranges_fit(in_off, in_len, 0, input.len()) || !ranges_fit(out_off, in_len, 0, out.len()) {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_agree()?;
+    let mut olen = vec![0u64; count];
+    check(unsafe {
+        ffi_agree::chipy_decode_ragged_dev(format, secret_key.as_ptr(), secret_key.len() as u64, input.as_ptr(),
+                                           in_off.as_ptr(), in_len.as_ptr(), count as u64, hashes.as_ptr(),
+                                           padding.as_ptr(), out.as_mut_ptr(), out_off.as_ptr(), olen.as_mut_ptr(),
+                                           status.as_mut_ptr() as *mut u32, scratch.ptr, stream.0)
+    })?;
+    Ok(olen)
+}
+
+/// Scratch of [`key_table_from_streams`] over the table `info` describes; 0 where the call would refuse it.
+pub fn key_table_from_streams_scratch_len(info: &TableInfo) -> u64 {
+    unsafe { ffi_agree::chipy_key_table_scratch_len(info) }
+}
+
+/// The key table of the resident level-13 streams a stream table describes,
+/// made without the host seeing a header or a key: what [`stream_keys`]
+/// followed by [`key_table`] produce, byte for byte, from a strict vouched
+/// planned read of every envelope's first 81 bytes and the key agreement
+/// kernels.  No copy back, no wait; the only upload is the secret.  Enqueued on
+/// `stream`.
+pub fn key_table_from_streams(stream_table: &DeviceBuffer, info: &TableInfo, secret_key: &[u8],
+                              table: &mut DeviceBuffer, scratch: &mut DeviceBuffer, stream: Stream) -> Result<()> {
+    let need = key_table_from_streams_scratch_len(info);
+    if (table.len() as u64) < key_table_len(info.nstreams) || (info.nstreams > 0 && need == 0) ||
+        (scratch.len() as u64) < need {
+        return Err(ChipError::InvalidArgument);
+    }
+    abi_agree()?;
+    check(unsafe {
+        ffi_agree::chipy_key_table_dev(stream_table.ptr, info, secret_key.as_ptr(), secret_key.len() as u64, table.ptr,
+                                       table.len() as u64, scratch.ptr, scratch.len() as u64, stream.0)
     })
 }
 

@@ -460,6 +460,30 @@ PAUDIT_SIGNATURES = {
                                                ctypes.c_void_p]),
 }
 
+# the agree header (include/carbonado_hip_agree.h): the Ecies key agreement on
+# the device and the envelope and one-call forms built on it, a fifteenth table
+# of its own
+AGREE_SIGNATURES = {
+    "chipy_abi_version": (ctypes.c_int, []),
+    "chipy_keys_scratch_len": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "chipy_seal_keys_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "chipy_open_keys_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "chipy_envelope_scratch_len": (ctypes.c_uint64, [c_u64p, ctypes.c_uint64]),
+    "chipy_seal_ragged_dev": ECIES_SIGNATURES["chipe_seal_ragged_dev"],
+    "chipy_open_ragged_dev": ECIES_SIGNATURES["chipe_open_ragged_dev"],
+    "chipy_encode_scratch_len": ECIES_SIGNATURES["chipe_encode_scratch_len"],
+    "chipy_decode_scratch_len": ECIES_SIGNATURES["chipe_decode_scratch_len"],
+    "chipy_encode_ragged_dev": ECIES_SIGNATURES["chipe_encode_ragged_dev"],
+    "chipy_decode_ragged_dev": ECIES_SIGNATURES["chipe_decode_ragged_dev"],
+    "chipy_key_table_scratch_len": (ctypes.c_uint64, [c_infop]),
+    "chipy_key_table_dev": (ctypes.c_int, [ctypes.c_void_p, c_infop, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                           ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+}
+
 _LIB = None
 
 
@@ -484,7 +508,7 @@ def lib() -> ctypes.CDLL:
                                   **READ_SIGNATURES, **VREAD_SIGNATURES, **ECIES_SIGNATURES,
                                   **SNAP_SIGNATURES, **CREAD_SIGNATURES, **FREAD_SIGNATURES,
                                   **QREAD_SIGNATURES, **KREAD_SIGNATURES, **GREAD_SIGNATURES,
-                                  **PAUDIT_SIGNATURES}.items():
+                                  **PAUDIT_SIGNATURES, **AGREE_SIGNATURES}.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

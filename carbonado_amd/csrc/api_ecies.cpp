@@ -2,7 +2,11 @@
 // device-resident messages.  The checks, the scratch layout and the table are
 // host code in ecies_plan.hpp; this file uploads the table (through a pinned
 // copy that a host function wipes behind the upload), enqueues the kernels of
-// ecies_kernels.hip and, last, the memset that zeroes the key region.
+// ecies_kernels.hip and, last, the memset that zeroes the key region.  The
+// envelope and one-call forms take the place the AES keys come from as a
+// parameter (api_agree.hpp): the stage pool's threads for the chipe_* calls,
+// the key agreement kernels for the chipy_* calls of api_agree.cpp.
+#include "api_agree.hpp"
 #include "api_common.hpp"
 #include "ecies_kernels.hpp"
 #include "ecies_plan.hpp"
@@ -33,9 +37,11 @@ GcmLaunch launch_of(const ecies::Plan &p, uint8_t *scr, const uint8_t *d_in, uin
     return L;
 }
 
-// env: the messages are envelopes (a seal scatters their header bytes)
+// env: the messages are envelopes (a seal scatters their header bytes);
+// upload: the table holds the keys and goes up here (else the key records are
+// on the device already, written by the key agreement kernels)
 int gcm_run(bool seal, ecies::Plan &p, const uint8_t *d_in, uint8_t *d_out, uint8_t *d_tag, uint32_t *d_status,
-            void *d_scratch, void *stream, bool env = false, bool keep_status = false) {
+            void *d_scratch, void *stream, bool env = false, bool keep_status = false, bool upload = true) {
     int st = use_device();
     if (st != CHIP_OK) {
         host::secure_wipe(p.table.data(), p.table.size());
@@ -43,7 +49,7 @@ int gcm_run(bool seal, ecies::Plan &p, const uint8_t *d_in, uint8_t *d_out, uint
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t *scr = static_cast<uint8_t *>(d_scratch);
-    CHIP_HIP(upload_key_table(p.table, scr, s));
+    if (upload) CHIP_HIP(upload_key_table(p.table, scr, s));
     GcmLaunch L = launch_of(p, scr, d_in, d_out, d_tag, d_status);
     L.keep_status = keep_status;
     hipError_t e = gcm_setup_launch(L, s);
@@ -60,6 +66,27 @@ int gcm_run(bool seal, ecies::Plan &p, const uint8_t *d_in, uint8_t *d_out, uint
     const hipError_t w = hipMemsetAsync(scr + p.lay.wipe_from(), 0, p.lay.wipe_len(), s);
     CHIP_HIP(e);
     CHIP_HIP(w);
+    return CHIP_OK;
+}
+
+// The tail of an envelope call whose keys the device derives: `derived` is what
+// became of the uploads and the key kernel; the GCM launches follow if it went
+// well, and both key regions are zeroed whatever happened.
+int gcm_run_derived(hipError_t derived, bool seal, ecies::Plan &p, const uint8_t *d_in, uint8_t *d_out, uint8_t *d_tag,
+                    uint32_t *d_status, void *d_scratch, void *stream, bool keep_status) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint8_t *scr = static_cast<uint8_t *>(d_scratch);
+    int st = CHIP_OK;
+    hipError_t w = hipSuccess;
+    if (derived == hipSuccess)
+        st = gcm_run(seal, p, d_in, d_out, d_tag, d_status, d_scratch, stream, seal, keep_status, false);
+    else
+        w = hipMemsetAsync(scr + p.lay.wipe_from(), 0, p.lay.wipe_len(), s);
+    const hipError_t wa = agree_wipe_enqueue(scr + p.lay.total, p.count, s);
+    CHIP_HIP(derived);
+    if (st != CHIP_OK) return st;
+    CHIP_HIP(w);
+    CHIP_HIP(wa);
     return CHIP_OK;
 }
 
@@ -104,9 +131,14 @@ int chipe_gcm_open_ragged_dev(const uint8_t *keys, const uint8_t *ivs, const uin
     return gcm_run(false, p, d_in, d_out, const_cast<uint8_t *>(d_tag), d_status, d_scratch, stream);
 }
 
-int chipe_seal_ragged_dev(const uint8_t *pubkey, uint64_t pubkey_len, const chip_ecies_inject *inject,
-                          const uint8_t *d_in, const uint64_t *in_off, const uint64_t *n, uint64_t count, uint8_t *d_out,
-                          const uint64_t *out_off, void *d_scratch, void *stream) {
+}  // extern "C"
+
+namespace chip {
+namespace api {
+
+int ecies_seal_env(KeySource src, const uint8_t *pubkey, uint64_t pubkey_len, const chip_ecies_inject *inject,
+                   const uint8_t *d_in, const uint64_t *in_off, const uint64_t *n, uint64_t count, uint8_t *d_out,
+                   const uint64_t *out_off, void *d_scratch, void *stream) {
     if (count == 0) return CHIP_OK;
     if (!pubkey || !in_off || !n || !out_off || !d_out || !d_scratch || count >= ecies::MAX_COUNT)
         return CHIP_ERR_INVALID_ARG;
@@ -127,6 +159,35 @@ int chipe_seal_ragged_dev(const uint8_t *pubkey, uint64_t pubkey_len, const chip
     uint8_t peer[65];
     st = host::ecies_peer(pubkey, pubkey_len, peer);
     if (st != CHIP_OK) return st;
+    if (src == KeySource::Device) {
+        // the host's share: the scalars and the nonces; the key records and header slots get their keys on the device
+        std::vector<uint8_t> words;
+        st = agree_draw(count, [&](uint64_t o) { return inject ? inject[o].ephemeral_sk : nullptr; }, &words);
+        const uint8_t none[65] = {0};
+        std::vector<uint8_t> ivs(16 * count);  // one RNG call for the batch
+        if (st == CHIP_OK && !agree_rand(ivs.data(), ivs.size())) st = CHIP_ERR_ECIES;
+        for (uint64_t o = 0; st == CHIP_OK && o < count; ++o) {
+            const uint8_t *iv = inject && inject[o].nonce ? inject[o].nonce : ivs.data() + 16 * o;
+            ecies::fill_key(p, o, none, iv);
+            ecies::fill_hdr(p, o, none, iv);
+        }
+        if (st == CHIP_OK) st = use_device();
+        Ctx *c = nullptr;
+        if (st == CHIP_OK) st = ctx_get(&c);
+        if (st != CHIP_OK) {
+            host::secure_wipe(words.data(), words.size());
+            return st;
+        }
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        uint8_t *scr = static_cast<uint8_t *>(d_scratch);
+        hipError_t e = h2d(c->stage, scr, p.table.data(), p.lay.upload_len(), s);  // public: no key in it
+        if (e == hipSuccess)
+            e = agree_seal_enqueue(c, peer, words, count, scr + p.lay.total, scr + p.lay.hdrs, ecies::HDR_PITCH,
+                                   scr + p.lay.keys, 48, s);
+        else
+            host::secure_wipe(words.data(), words.size());
+        return gcm_run_derived(e, true, p, d_in, d_out, d_out, nullptr, d_scratch, stream, false);
+    }
     st = use_device();
     if (st != CHIP_OK) return st;
     // the key agreement of every object (two scalar multiplications each), then its slots of the table
@@ -154,9 +215,9 @@ int chipe_seal_ragged_dev(const uint8_t *pubkey, uint64_t pubkey_len, const chip
     return gcm_run(true, p, d_in, d_out, d_out, nullptr, d_scratch, stream, true);
 }
 
-static int open_env(const uint8_t *secret_key, uint64_t sk_len, const uint8_t *d_in, const uint64_t *in_off,
-                    const uint64_t *in_len, uint64_t count, uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len,
-                    uint32_t *d_status, void *d_scratch, void *stream, bool keep_status, bool check_only) {
+int ecies_open_env(KeySource src, const uint8_t *secret_key, uint64_t sk_len, const uint8_t *d_in, const uint64_t *in_off,
+                   const uint64_t *in_len, uint64_t count, uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len,
+                   uint32_t *d_status, void *d_scratch, void *stream, bool keep_status, bool check_only) {
     if (count == 0) return CHIP_OK;
     if (!secret_key || !d_in || !in_off || !in_len || !out_off || !out_len || !d_status || !d_scratch ||
         count >= ecies::MAX_COUNT)
@@ -188,11 +249,26 @@ static int open_env(const uint8_t *secret_key, uint64_t sk_len, const uint8_t *d
     if (st != CHIP_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint8_t *scr = static_cast<uint8_t *>(d_scratch);
-    // the public part of the table, the header bytes of every envelope gathered behind it, one copy back:
-    // the keys depend on them, so the call waits here
+    // the public part of the table, the header bytes of every envelope gathered behind it
     CHIP_HIP(h2d(c->stage, scr, p.table.data(), p.lay.hdrs, s));
     const GcmLaunch G = launch_of(p, scr, d_in, d_out, const_cast<uint8_t *>(d_in), d_status);
     CHIP_HIP(gcm_hdr_launch(G, scr + p.lay.hdrs, false, s));
+    if (src == KeySource::Device) {
+        // the key kernel reads the header slots, writes the key records and refuses what does not parse
+        AgreeOpen A{};
+        A.count = uint32_t(count);
+        A.eph = scr + p.lay.hdrs;
+        A.eph_pitch = ecies::HDR_PITCH;
+        A.keys = scr + p.lay.keys;
+        A.key_pitch = 48;
+        A.refused = scr + p.lay.msgs + offsetof(gcm::Msg, refused);
+        A.refused_stride = sizeof(gcm::Msg);
+        A.copy_iv = 1;
+        const hipError_t e = agree_open_enqueue(secret_key, scr + p.lay.total, A, s);
+        return gcm_run_derived(e, false, p, d_in, d_out, const_cast<uint8_t *>(d_in), d_status, d_scratch, stream,
+                               keep_status);
+    }
+    // one copy back: the keys depend on the header bytes, so the call waits here
     std::vector<uint8_t> hdrs(count * ecies::HDR_PITCH);
     CHIP_HIP(d2h(c->stage, hdrs.data(), scr + p.lay.hdrs, hdrs.size(), s));
     for_objects(count, [&](uint64_t o) {
@@ -208,12 +284,26 @@ static int open_env(const uint8_t *secret_key, uint64_t sk_len, const uint8_t *d
     return gcm_run(false, p, d_in, d_out, const_cast<uint8_t *>(d_in), d_status, d_scratch, stream, false, keep_status);
 }
 
+}  // namespace api
+}  // namespace chip
+
+extern "C" {
+
+int chipe_seal_ragged_dev(const uint8_t *pubkey, uint64_t pubkey_len, const chip_ecies_inject *inject,
+                          const uint8_t *d_in, const uint64_t *in_off, const uint64_t *n, uint64_t count, uint8_t *d_out,
+                          const uint64_t *out_off, void *d_scratch, void *stream) {
+    return ecies_seal_env(KeySource::Host, pubkey, pubkey_len, inject, d_in, in_off, n, count, d_out, out_off, d_scratch,
+                          stream);
+}
+
 int chipe_open_ragged_dev(const uint8_t *secret_key, uint64_t sk_len, const uint8_t *d_in, const uint64_t *in_off,
                           const uint64_t *in_len, uint64_t count, uint8_t *d_out, const uint64_t *out_off,
                           uint64_t *out_len, uint32_t *d_status, void *d_scratch, void *stream) {
-    return open_env(secret_key, sk_len, d_in, in_off, in_len, count, d_out, out_off, out_len, d_status, d_scratch, stream,
-                    false, false);
+    return ecies_open_env(KeySource::Host, secret_key, sk_len, d_in, in_off, in_len, count, d_out, out_off, out_len,
+                          d_status, d_scratch, stream, false, false);
 }
+
+}  // extern "C"
 
 // ---- formats 5, 9, 13: Ecies with Bao and / or Zfec, one call ---------------------
 namespace {
@@ -222,20 +312,22 @@ bool ecies_format(uint8_t f) {
     return f < 16 && (f & CHIP_FORMAT_ECIES) && !(f & CHIP_FORMAT_SNAPPY) && (f & (CHIP_FORMAT_BAO | CHIP_FORMAT_ZFEC));
 }
 
-// Scratch of the one-call forms: envelopes (row o of up16(bound[o]) bytes) | GCM scratch | ragged scratch.
+// Scratch of the one-call forms: envelopes (row o of up16(bound[o]) bytes) | GCM scratch (with the agreement's
+// behind it when the device derives the keys) | ragged scratch.
 struct Regions {
     std::vector<uint64_t> env_off;
     uint64_t gcm = 0, ragged = 0, total = 0;
 };
-bool regions(uint8_t f12, const uint64_t *plain_bound, const uint64_t *env_bound, const uint64_t *ragged_len,
-             uint64_t count, bool decode, Regions *r) {
+bool regions(KeySource src, uint8_t f12, const uint64_t *plain_bound, const uint64_t *env_bound,
+             const uint64_t *ragged_len, uint64_t count, bool decode, Regions *r) {
     r->env_off.resize(count);
     uint64_t at = 0;
     for (uint64_t o = 0; o < count; ++o) {
         r->env_off[o] = at;
         at += ecies::up16(env_bound[o]);
     }
-    const uint64_t g = ecies::gcm_scratch_len(plain_bound, count);
+    const uint64_t g = src == KeySource::Device ? chipy_envelope_scratch_len(plain_bound, count)
+                                                : ecies::gcm_scratch_len(plain_bound, count);
     const uint64_t x = chipx_ragged_scratch_len(f12, ragged_len, count, decode);
     if (!g) return false;
     r->gcm = at;
@@ -246,24 +338,27 @@ bool regions(uint8_t f12, const uint64_t *plain_bound, const uint64_t *env_bound
 
 }  // namespace
 
-uint64_t chipe_encode_scratch_len(uint8_t format, const uint64_t *n, uint64_t count) {
+namespace chip {
+namespace api {
+
+uint64_t ecies_encode_scratch_len(KeySource src, uint8_t format, const uint64_t *n, uint64_t count) {
     if (!ecies_format(format) || !n || count == 0 || count >= ecies::MAX_COUNT) return 0;
     std::vector<uint64_t> env(count);
     for (uint64_t o = 0; o < count; ++o) env[o] = n[o] + ecies::ENV_OVERHEAD;
     Regions r;
-    return regions(format & 12, n, env.data(), env.data(), count, false, &r) ? r.total : 0;
+    return regions(src, format & 12, n, env.data(), env.data(), count, false, &r) ? r.total : 0;
 }
 
-uint64_t chipe_decode_scratch_len(uint8_t format, const uint64_t *in_len, uint64_t count) {
+uint64_t ecies_decode_scratch_len(KeySource src, uint8_t format, const uint64_t *in_len, uint64_t count) {
     if (!ecies_format(format) || !in_len || count == 0 || count >= ecies::MAX_COUNT) return 0;
     Regions r;  // a stream is longer than what it decodes to: its length bounds the envelope and the plaintext
-    return regions(format & 12, in_len, in_len, in_len, count, true, &r) ? r.total : 0;
+    return regions(src, format & 12, in_len, in_len, in_len, count, true, &r) ? r.total : 0;
 }
 
-int chipe_encode_ragged_dev(uint8_t format, const uint8_t *pubkey, uint64_t pubkey_len, const chip_ecies_inject *inject,
-                            const uint8_t *d_in, const uint64_t *in_off, const uint64_t *n, uint64_t count,
-                            uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len, uint8_t *d_hash,
-                            chip_encode_info *info, void *d_scratch, void *stream) {
+int ecies_encode_env(KeySource src, uint8_t format, const uint8_t *pubkey, uint64_t pubkey_len,
+                     const chip_ecies_inject *inject, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *n,
+                     uint64_t count, uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len, uint8_t *d_hash,
+                     chip_encode_info *info, void *d_scratch, void *stream) {
     if (!ecies_format(format)) return CHIP_ERR_INVALID_ARG;
     if (count == 0) return CHIP_OK;
     if (!pubkey || !in_off || !n || !out_off || !out_len || !d_out || !d_hash || !d_scratch || misaligned16(d_scratch) ||
@@ -276,7 +371,7 @@ int chipe_encode_ragged_dev(uint8_t format, const uint8_t *pubkey, uint64_t pubk
         env_len[o] = n[o] + ecies::ENV_OVERHEAD;
     }
     Regions r;
-    if (!regions(f12, n, env_len.data(), env_len.data(), count, false, &r)) return CHIP_ERR_INVALID_ARG;
+    if (!regions(src, f12, n, env_len.data(), env_len.data(), count, false, &r)) return CHIP_ERR_INVALID_ARG;
     uint8_t *scr = static_cast<uint8_t *>(d_scratch);
     {  // the level-12 half's own checks, before anything is enqueued
         ragged::Plan rp;
@@ -284,8 +379,8 @@ int chipe_encode_ragged_dev(uint8_t format, const uint8_t *pubkey, uint64_t pubk
                                      reinterpret_cast<uintptr_t>(d_out), out_off, out_len, &rp);
         if (st != CHIP_OK) return st;
     }
-    int st = chipe_seal_ragged_dev(pubkey, pubkey_len, inject, d_in, in_off, n, count, scr, r.env_off.data(),
-                                   scr + r.gcm, stream);
+    int st = ecies_seal_env(src, pubkey, pubkey_len, inject, d_in, in_off, n, count, scr, r.env_off.data(), scr + r.gcm,
+                            stream);
     if (st != CHIP_OK) return st;
     st = chipx_encode_ragged_dev(f12, scr, r.env_off.data(), env_len.data(), count, d_out, out_off, out_len, d_hash,
                                  nullptr, scr + r.ragged, stream);
@@ -298,10 +393,10 @@ int chipe_encode_ragged_dev(uint8_t format, const uint8_t *pubkey, uint64_t pubk
     return CHIP_OK;
 }
 
-int chipe_decode_ragged_dev(uint8_t format, const uint8_t *secret_key, uint64_t sk_len, const uint8_t *d_in,
-                            const uint64_t *in_off, const uint64_t *in_len, uint64_t count, const uint8_t *d_hash,
-                            const uint32_t *padding, uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len,
-                            uint32_t *d_status, void *d_scratch, void *stream) {
+int ecies_decode_env(KeySource src, uint8_t format, const uint8_t *secret_key, uint64_t sk_len, const uint8_t *d_in,
+                     const uint64_t *in_off, const uint64_t *in_len, uint64_t count, const uint8_t *d_hash,
+                     const uint32_t *padding, uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len,
+                     uint32_t *d_status, void *d_scratch, void *stream) {
     if (!ecies_format(format)) return CHIP_ERR_INVALID_ARG;
     if (count == 0) return CHIP_OK;
     if (!secret_key || !d_in || !in_off || !in_len || !out_off || !out_len || !d_status || !d_scratch ||
@@ -309,7 +404,7 @@ int chipe_decode_ragged_dev(uint8_t format, const uint8_t *secret_key, uint64_t 
         return CHIP_ERR_INVALID_ARG;
     const uint8_t f12 = format & 12;
     Regions r;
-    if (!regions(f12, in_len, in_len, in_len, count, true, &r)) return CHIP_ERR_INVALID_ARG;
+    if (!regions(src, f12, in_len, in_len, in_len, count, true, &r)) return CHIP_ERR_INVALID_ARG;
     uint8_t *scr = static_cast<uint8_t *>(d_scratch);
     std::vector<uint64_t> env_len(count);
     {  // both halves' checks, before anything is enqueued
@@ -318,15 +413,44 @@ int chipe_decode_ragged_dev(uint8_t format, const uint8_t *secret_key, uint64_t 
                                      reinterpret_cast<uintptr_t>(scr), r.env_off.data(), env_len.data(), &rp);
         if (st != CHIP_OK) return st;
         if ((f12 & CHIP_FORMAT_BAO) && !d_hash) return CHIP_ERR_HASH_DECODE;
-        st = open_env(secret_key, sk_len, scr, r.env_off.data(), env_len.data(), count, d_out, out_off, out_len, d_status,
-                      scr + r.gcm, stream, true, true);
+        st = ecies_open_env(src, secret_key, sk_len, scr, r.env_off.data(), env_len.data(), count, d_out, out_off, out_len,
+                            d_status, scr + r.gcm, stream, true, true);
         if (st != CHIP_OK) return st;
     }
     int st = chipx_decode_ragged_dev(f12, d_in, in_off, in_len, count, d_hash, padding, scr, r.env_off.data(),
                                      env_len.data(), d_status, scr + r.ragged, stream);
     if (st != CHIP_OK) return st;
-    return open_env(secret_key, sk_len, scr, r.env_off.data(), env_len.data(), count, d_out, out_off, out_len, d_status,
-                    scr + r.gcm, stream, true, false);
+    return ecies_open_env(src, secret_key, sk_len, scr, r.env_off.data(), env_len.data(), count, d_out, out_off, out_len,
+                          d_status, scr + r.gcm, stream, true, false);
+}
+
+}  // namespace api
+}  // namespace chip
+
+extern "C" {
+
+uint64_t chipe_encode_scratch_len(uint8_t format, const uint64_t *n, uint64_t count) {
+    return ecies_encode_scratch_len(KeySource::Host, format, n, count);
+}
+
+uint64_t chipe_decode_scratch_len(uint8_t format, const uint64_t *in_len, uint64_t count) {
+    return ecies_decode_scratch_len(KeySource::Host, format, in_len, count);
+}
+
+int chipe_encode_ragged_dev(uint8_t format, const uint8_t *pubkey, uint64_t pubkey_len, const chip_ecies_inject *inject,
+                            const uint8_t *d_in, const uint64_t *in_off, const uint64_t *n, uint64_t count,
+                            uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len, uint8_t *d_hash,
+                            chip_encode_info *info, void *d_scratch, void *stream) {
+    return ecies_encode_env(KeySource::Host, format, pubkey, pubkey_len, inject, d_in, in_off, n, count, d_out, out_off,
+                            out_len, d_hash, info, d_scratch, stream);
+}
+
+int chipe_decode_ragged_dev(uint8_t format, const uint8_t *secret_key, uint64_t sk_len, const uint8_t *d_in,
+                            const uint64_t *in_off, const uint64_t *in_len, uint64_t count, const uint8_t *d_hash,
+                            const uint32_t *padding, uint8_t *d_out, const uint64_t *out_off, uint64_t *out_len,
+                            uint32_t *d_status, void *d_scratch, void *stream) {
+    return ecies_decode_env(KeySource::Host, format, secret_key, sk_len, d_in, in_off, in_len, count, d_hash, padding,
+                            d_out, out_off, out_len, d_status, d_scratch, stream);
 }
 
 }  // extern "C"

@@ -946,6 +946,134 @@ def decode_ragged_ecies(fmt: int, secret_key: bytes, enc: torch.Tensor, in_off, 
     return olen.tolist()
 
 
+# ---- the Ecies key agreement on the device (include/carbonado_hip_agree.h):
+# secp256k1 and HKDF-SHA256 kernels, and the envelope and one-call forms above
+# with no host key agreement, no copy back and no wait
+
+def agree_scratch(count: int, device=None) -> torch.Tensor:
+    """Scratch of a seal_keys / open_keys call over count objects."""
+    return _scratch(_lib.lib().chipy_keys_scratch_len(count), device)
+
+
+def envelope_scratch(n, device=None) -> torch.Tensor:
+    """Scratch of ecies_seal_ragged_dev_keys / ecies_open_ragged_dev_keys over plaintexts of n[o] bytes."""
+    ln, pln, count = _arr(n)
+    return _scratch(_lib.lib().chipy_envelope_scratch_len(pln, count), device)
+
+
+def _pitched(buf: torch.Tensor, pitch: int, width: int, count: int) -> None:
+    """count slots of `width` bytes at a pitch lie inside a flat device buffer"""
+    _flat(buf)
+    assert count == 0 or (pitch >= width and buf.numel() >= (count - 1) * pitch + width)
+
+
+def seal_keys(pubkey: bytes, count: int, pub: torch.Tensor, pub_pitch: int, keys: torch.Tensor, key_pitch: int,
+              scratch: torch.Tensor, eph_sk=None) -> None:
+    """Per object o: the ephemeral public key k_o G (0x04 || x || y) to
+    pub[o * pub_pitch :][:65] and the AES key HKDF(E65 || (k_o P)65) to
+    keys[o * key_pitch :][:32], P the receiver `pubkey` (33 or 65 bytes).
+    eph_sk: None (the library's RNG) or 32 * count host bytes.  The keys stay
+    in `keys`: the caller wipes them.  Enqueued on the current stream, not
+    synchronised."""
+    _pitched(pub, pub_pitch, 65, count)
+    _pitched(keys, key_pitch, 32, count)
+    _resident(scratch)
+    sk, psk, nsk = _arr(np.frombuffer(bytes(eph_sk or b""), dtype=np.uint8), np.uint8)
+    assert eph_sk is None or nsk == 32 * count
+    check(_lib.lib().chipy_seal_keys_dev(bytes(pubkey), len(pubkey),
+                                         ctypes.cast(psk, ctypes.c_void_p) if eph_sk is not None else None, count,
+                                         _p(pub), pub_pitch, _p(keys), key_pitch, _p(scratch), scratch.numel(),
+                                         _stream()))
+
+
+def open_keys(secret_key: bytes, eph: torch.Tensor, eph_pitch: int, count: int, keys: torch.Tensor, key_pitch: int,
+              status: torch.Tensor, scratch: torch.Tensor) -> None:
+    """Per object o: the AES key HKDF(R65 || (sk R)65) of the ephemeral key
+    R = eph[o * eph_pitch :][:65] to keys[o * key_pitch :][:32], status[o] = 0;
+    or ECIES_FAILED and a key of zeros for an R that does not parse.  The keys
+    stay in `keys`: the caller wipes them.  Enqueued on the current stream, not
+    synchronised."""
+    _pitched(eph, eph_pitch, 65, count)
+    _pitched(keys, key_pitch, 32, count)
+    _resident(scratch)
+    _words(count, status)
+    check(_lib.lib().chipy_open_keys_dev(bytes(secret_key), len(secret_key), _p(eph), eph_pitch, count, _p(keys),
+                                         key_pitch, _p(status), _p(scratch), scratch.numel(), _stream()))
+
+
+def ecies_seal_ragged_dev_keys(pubkey: bytes, inp: torch.Tensor, in_off, n, out: torch.Tensor, out_off,
+                               scratch: torch.Tensor, inject=None) -> None:
+    """ecies_seal_ragged with the key agreement on the device: the same
+    envelopes for the same injected values, no host elliptic-curve work.
+    scratch: envelope_scratch(n)."""
+    _flat(inp, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff), (pioff, pln, pooff), count = _ragged(inp, in_off, n, out, out_off,
+                                                           room=lambda ln: ln + np.uint64(97))
+    assert scratch.numel() >= _lib.lib().chipy_envelope_scratch_len(pln, count)
+    inj, keep = _inject_array(inject, count)
+    check(_lib.lib().chipy_seal_ragged_dev(bytes(pubkey), len(pubkey), inj, _p(inp), pioff, pln, count, _p(out), pooff,
+                                           _p(scratch), _stream()))
+
+
+def ecies_open_ragged_dev_keys(secret_key: bytes, inp: torch.Tensor, in_off, in_len, out: torch.Tensor, out_off,
+                               status: torch.Tensor, scratch: torch.Tensor):
+    """ecies_open_ragged with the key agreement on the device: no copy back
+    and no wait.  scratch: envelope_scratch of the plaintext lengths.  Returns
+    the plaintext length per object."""
+    _flat(inp, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff), (pioff, pln, pooff), count = _ragged(inp, in_off, in_len, out, out_off, room=_plain_lens)
+    _words(count, status)
+    pl, ppl, _ = _arr(_plain_lens(ln))
+    assert scratch.numel() >= _lib.lib().chipy_envelope_scratch_len(ppl, count)
+    olen, polen = _out(count)
+    check(_lib.lib().chipy_open_ragged_dev(bytes(secret_key), len(secret_key), _p(inp), pioff, pln, count, _p(out),
+                                           pooff, polen, _p(status), _p(scratch), _stream()))
+    return olen.tolist()
+
+
+def ecies_ragged_scratch_dev_keys(fmt: int, lens, decode: bool = False, device=None) -> torch.Tensor:
+    """Scratch of encode_ragged_ecies_dev_keys (object lengths) / decode_ragged_ecies_dev_keys (stream lengths)."""
+    ln, pln, count = _arr(lens)
+    fn = _lib.lib().chipy_decode_scratch_len if decode else _lib.lib().chipy_encode_scratch_len
+    return _scratch(fn(fmt, pln, count), device)
+
+
+def encode_ragged_ecies_dev_keys(fmt: int, pubkey: bytes, inp: torch.Tensor, in_off, sizes, out: torch.Tensor, out_off,
+                                 hashes: torch.Tensor, scratch: torch.Tensor, inject=None):
+    """encode_ragged_ecies with the key agreement on the device.  Returns
+    (encoded length per object, EncodeInfo per object)."""
+    _flat(inp, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff), (pioff, pln, pooff), count = _ragged(inp, in_off, sizes, out, out_off, room=None)
+    _hashes(hashes, count)
+    assert scratch.numel() >= _lib.lib().chipy_encode_scratch_len(fmt, pln, count)
+    inj, keep = _inject_array(inject, count)
+    olen, polen, info = _encode_outputs(count)
+    check(_lib.lib().chipy_encode_ragged_dev(fmt, bytes(pubkey), len(pubkey), inj, _p(inp), pioff, pln, count, _p(out),
+                                             pooff, polen, _p(hashes), info, _p(scratch), _stream()))
+    return _encoded(olen, info, ooff, out)
+
+
+def decode_ragged_ecies_dev_keys(fmt: int, secret_key: bytes, enc: torch.Tensor, in_off, in_len, hashes: torch.Tensor,
+                                 padding, out: torch.Tensor, out_off, status: torch.Tensor, scratch: torch.Tensor):
+    """decode_ragged_ecies with the key agreement on the device: the call no
+    longer blocks.  Returns the plaintext length per object."""
+    _flat(enc, out, one_dim=False)
+    _resident(scratch)
+    (ioff, ln, ooff, pad), (pioff, pln, pooff, ppad), count = _ragged(enc, in_off, in_len, out, out_off, padding,
+                                                                      kinds="I", room=None)
+    _words(count, status)
+    assert scratch.numel() >= _lib.lib().chipy_decode_scratch_len(fmt, pln, count)
+    olen, polen = _out(count)
+    check(_lib.lib().chipy_decode_ragged_dev(fmt, bytes(secret_key), len(secret_key), _p(enc), pioff, pln, count,
+                                             _p(hashes) if hashes is not None else None, ppad, _p(out), pooff,
+                                             polen, _p(status), _p(scratch), _stream()))
+    assert _fits(ooff, olen, out.numel())
+    return olen.tolist()
+
+
 # ---- plaintext ranged reads of level-13 streams (include/carbonado_hip_cread.h):
 # the keystream over ranges, the keys of resident streams, the read
 
@@ -1101,6 +1229,26 @@ def read_plain_ranges_planned(table: StreamTable, key_table: KeyTable, req_strea
                                            key_table.table.numel(), _p(req_stream), _p(start), _p(length), nreq,
                                            max_len, _p(content), content_stride, _p(content_len), _p(status),
                                            _p(used), _p(vouch), flags, _p(scratch), scratch.numel(), _stream()))
+
+
+def key_table_from_streams(table: StreamTable, secret_key: bytes, scratch: torch.Tensor | None = None) -> KeyTable:
+    """The key table of the resident level-13 streams `table` describes, made
+    without the host seeing a header or a key: what stream_keys followed by
+    key_table produce, byte for byte, from a strict vouched planned read of
+    every envelope's first 81 bytes and the key agreement kernels
+    (include/carbonado_hip_agree.h).  No copy back, no wait; the only upload is
+    the secret.  Enqueued on the current stream; the scratch (made here unless
+    given) must outlive the enqueued work."""
+    need = _lib.lib().chipy_key_table_scratch_len(ctypes.byref(table.info))
+    if table.nstreams and not need:
+        raise ValueError("the call would refuse this table")
+    if scratch is None:
+        scratch = _scratch(need, table.table.device)
+    _resident(scratch)
+    kt = torch.empty(_lib.lib().chipk_key_table_len(table.nstreams), dtype=torch.uint8, device=table.table.device)
+    check(_lib.lib().chipy_key_table_dev(_p(table.table), ctypes.byref(table.info), bytes(secret_key), len(secret_key),
+                                         _p(kt), kt.numel(), _p(scratch), scratch.numel(), _stream()))
+    return KeyTable(kt, table.nstreams)
 
 
 # ---- snappy on the device (include/carbonado_hip_snap.h): the framing format
