@@ -287,7 +287,7 @@ int chipy_key_table_dev(const void *d_table, const chipq_table_info *info, const
     A.eph = scr + lay.hdrs;
     A.eph_pitch = ecies::HDR_PITCH;
     A.keys = tab + tl.raw;
-    A.key_pitch = kread::RAW_KEY;
+    A.key_pitch = cread::RAW_KEY;
     A.status = key_status;
     A.copy_iv = 1;
     A.gate = words(lay.status);

@@ -1,9 +1,11 @@
-// audit_checks.hpp — the per-node checks of a slice request as device
-// functions, shared by KA (audit_kernels.hip) and the gated checks of the
-// ranged reads (read_kernels.hip): a work item's request by binary search in a
-// prefix array, one selected parent on a lane, one selected chunk on a quad of
-// lanes (quad_b3.hpp).  The kernels around them decide which items run and
-// what a mismatch flags.
+// audit_checks.hpp — what a slice audit does with one work item of a request,
+// as device functions: one selected parent on a lane, one selected chunk on a
+// quad of lanes (quad_b3.hpp), shared by KA (audit_kernels.hip), KB
+// (paudit_kernels.hip) and the gated checks of the ranged reads
+// (read_kernels.hip, vread_kernels.hip, qread_kernels.hip); 16 B of the
+// content and of the proof gather on a lane, shared by KA and KB.  The kernels
+// around them find a work item's request (a prefix search, slot arithmetic)
+// and decide which items run and what a mismatch flags.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -107,6 +109,47 @@ __device__ __forceinline__ bool chunk_ok(const Req &a, uint64_t k, uint32_t (&ms
         ok &= want[q] == h0 && want[4 + q] == h1;
     }
     return ok;
+}
+
+// ---- the gathers, 16 B per lane ---------------------------------------------------
+// content bytes [o, o + 16) of request a (o < a.olen, 16 | o), the last unit
+// short: the verified bytes where the request's status word stayed 0, zeros
+// otherwise.  Content starts at the first selected chunk; 16 | 1024: a unit
+// sits in one chunk.
+template <bool PROOF>
+__device__ __forceinline__ void content_unit(const Req &a, uint64_t o, uint32_t status) {
+    const uint64_t left = a.olen - o;
+    uint8_t *dst = reinterpret_cast<uint8_t *>(a.dst) + o;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (status == 0) {
+        const uint8_t *p = reinterpret_cast<const uint8_t *>(a.src) +
+                           node_off<PROOF>(a.first + o / 1024, 0, a.N, a.first, a.last) + o % 1024;
+        v = left >= 16 ? load16_a8(p) : load16_partial(p, (uint32_t)left);
+    }
+    if (left >= 16) *glb(reinterpret_cast<u32x4 *>(dst)) = v;
+    else store16_partial(dst, v, (uint32_t)left);
+}
+
+// the proof of request a, from its stream into its packed pre-order: the
+// length header as stored, 16-B unit q < 4 of the k-th selected parent, 16-B
+// unit q < 64 of the k-th selected chunk (nothing past a short last chunk)
+__device__ __forceinline__ void proof_header(const Req &a) {
+    *glb(reinterpret_cast<uint64_t *>(a.dst)) = *reinterpret_cast<const uint64_t *>(a.src);
+}
+__device__ __forceinline__ void proof_parent_unit(const Req &a, uint64_t k, uint64_t q) {
+    uint64_t s = 0;
+    const int lv = parent_item(a.N, a.first, a.last, k, &s);
+    const uint64_t w = 16 * q;
+    store16_a8<false>(reinterpret_cast<uint8_t *>(a.dst) + proof_off(s, lv, a.N, a.first, a.last) + w,
+                      load16_a8(reinterpret_cast<const uint8_t *>(a.src) + stream_off(s, lv, a.N) + w));
+}
+__device__ __forceinline__ void proof_chunk_unit(const Req &a, uint64_t k, uint64_t q) {
+    const uint64_t c = a.first + k, w = 16 * q, clen = chunk_len(c, a.n);
+    if (w >= clen) return;  // past a short last chunk
+    const uint8_t *p = reinterpret_cast<const uint8_t *>(a.src) + stream_off(c, 0, a.N) + w;
+    uint8_t *d = reinterpret_cast<uint8_t *>(a.dst) + proof_off(c, 0, a.N, a.first, a.last) + w;
+    if (w + 16 <= clen) store16_a8<false>(d, load16_a8(p));
+    else store16_partial(d, load16_partial(p, (uint32_t)(clen - w)), (uint32_t)(clen - w));
 }
 
 }  // namespace audit

@@ -74,16 +74,7 @@ __global__ __launch_bounds__(TPB) void audit_content_kernel(const Req *reqs, con
     if (i >= total) return;
     const uint32_t r = prefix_find(pre, nreq, i);
     const Req a = reqs[r];
-    const uint64_t o = UNIT * (i - pre[r]), left = a.olen - o;  // content bytes [o, o + 16) of the request
-    uint8_t *dst = reinterpret_cast<uint8_t *>(a.dst) + o;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (status[r] == 0) {  // content starts at the first selected chunk; 16 | 1024: a unit sits in one chunk
-        const uint8_t *p = reinterpret_cast<const uint8_t *>(a.src) +
-                           node_off<PROOF>(a.first + o / 1024, 0, a.N, a.first, a.last) + o % 1024;
-        v = left >= 16 ? load16_a8(p) : load16_partial(p, (uint32_t)left);
-    }
-    if (left >= 16) *glb(reinterpret_cast<u32x4 *>(dst)) = v;
-    else store16_partial(dst, v, (uint32_t)left);
+    content_unit<PROOF>(a, UNIT * (i - pre[r]), status[r]);
 }
 
 __global__ __launch_bounds__(TPB) void audit_extract_kernel(const Req *reqs, const uint64_t *pre,
@@ -92,29 +83,13 @@ __global__ __launch_bounds__(TPB) void audit_extract_kernel(const Req *reqs, con
     if (i >= total) return;
     const uint32_t r = prefix_find(pre, nreq, i);
     const Req a = reqs[r];
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(a.src);
-    uint8_t *dst = reinterpret_cast<uint8_t *>(a.dst);
-    uint64_t u = i - pre[r];
-    if (u == 0) {  // the length header, as stored
-        *glb(reinterpret_cast<uint64_t *>(dst)) = *reinterpret_cast<const uint64_t *>(src);
-        return;
-    }
+    uint64_t u = i - pre[r];  // the request's units: the header, 4 per parent, 64 per chunk
+    if (u == 0) return proof_header(a);
     u -= 1;
     const uint64_t np = parents[r + 1] - parents[r];
-    if (u < 4 * np) {  // 16 B of a parent
-        uint64_t s = 0;
-        const int lv = parent_item(a.N, a.first, a.last, u / 4, &s);
-        const uint64_t w = 16 * (u % 4);
-        store16_a8<false>(dst + proof_off(s, lv, a.N, a.first, a.last) + w, load16_a8(src + stream_off(s, lv, a.N) + w));
-        return;
-    }
+    if (u < 4 * np) return proof_parent_unit(a, u / 4, u % 4);
     u -= 4 * np;
-    const uint64_t c = a.first + u / 64, w = 16 * (u % 64), clen = chunk_len(c, a.n);
-    if (w >= clen) return;  // past a short last chunk
-    const uint8_t *p = src + stream_off(c, 0, a.N) + w;
-    uint8_t *d = dst + proof_off(c, 0, a.N, a.first, a.last) + w;
-    if (w + 16 <= clen) store16_a8<false>(d, load16_a8(p));
-    else store16_partial(d, load16_partial(p, (uint32_t)(clen - w)), (uint32_t)(clen - w));
+    proof_chunk_unit(a, u / 64, u % 64);
 }
 
 }  // namespace audit

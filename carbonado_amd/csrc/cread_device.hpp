@@ -32,6 +32,7 @@ namespace cread {
 constexpr uint32_t LANES = gcm::LANES;
 constexpr uint32_t SPAN_UNITS = 2 * LANES - 1;  // units of a work item
 constexpr uint64_t MAX_END = (uint64_t(1) << 36) - 32;  // GCM's limit on one message
+constexpr uint64_t RAW_KEY = 48;  // a raw key record: key (32) || IV (16), as ctr_setup_kernel reads it
 
 // What a read needs of a key: no power of H (a read hashes nothing with it).
 struct CtrKey {
@@ -155,6 +156,20 @@ GCM_HD void lane_zero(const Item &it, uint32_t span, uint32_t lane, uint8_t *buf
         const uint64_t left = it.n - 16 * (u0 + x);
         gcm::store_block(buf + 16 * (u0 + x), z, uint32_t(left < 16 ? left : 16));
     }
+}
+// a killed item on one lane: no keystream, zeros over the lane's units, and by
+// span 0 the item's result words, i its index in them.  KC's wave finds the
+// item in its table, KK's builds it from the request; both end here.  Plain
+// stores and no lane exchange, so it stands with the other lane functions and
+// the host check runs it.
+GCM_HD void lane_kill(const Item &it, uint32_t span, uint32_t lane, uint8_t *buf, uint32_t *status, uint32_t *used,
+                      uint32_t *vouch, uint32_t i) {
+    if (span == 0 && lane == 0) {
+        status[i] = it.kill;
+        used[i] = 0;
+        vouch[i] = 0;
+    }
+    lane_zero(it, span, lane, buf);
 }
 
 // the item of work item w: the last one whose work0 is not behind it (items

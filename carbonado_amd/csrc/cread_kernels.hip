@@ -22,7 +22,7 @@ __global__ __launch_bounds__(64) void ctr_setup_kernel(const uint8_t *__restrict
     __shared__ uint32_t rk[gcm::RK_WORDS];
     __shared__ uint32_t j0[4];
     const uint32_t o = blockIdx.x, lane = threadIdx.x;
-    if (lane < 12) kiv[lane] = reinterpret_cast<const uint32_t *>(raw + 48ull * o)[lane];
+    if (lane < 12) kiv[lane] = reinterpret_cast<const uint32_t *>(raw + RAW_KEY * o)[lane];
     __syncthreads();
     if (lane == 0) {
         gcm::aes256_expand(reinterpret_cast<const uint8_t *>(kiv), w, rk);
@@ -42,12 +42,7 @@ __global__ __launch_bounds__(256) void ctr_range_kernel(CtrLaunch L) {
     const uint32_t span = w - it.work0;
     uint8_t *buf = L.buf + it.buf_off;
     if (it.kill) {  // decided on the host: no keystream, no gate
-        if (span == 0 && lane == 0) {
-            L.status[i] = it.kill;
-            L.used[i] = 0;
-            L.vouch[i] = 0;
-        }
-        lane_zero(it, span, lane, buf);
+        lane_kill(it, span, lane, buf, L.status, L.used, L.vouch, i);
         return;
     }
     if (L.gate && __builtin_amdgcn_readfirstlane(L.gate[i]) != 0) return;

@@ -6,7 +6,7 @@
 //
 // Scratch of a call, in this order (every region 16-B aligned):
 //   items  [nitems]  cread::Item    public: offsets, positions, lengths, work ranges
-//   keys   [nkeys]   48 B           key (32) || IV (16) of the keys some item uses
+//   keys   [nkeys]   RAW_KEY (48) B key (32) || IV (16) of the keys some item uses
 //   km     [nkeys]   cread::CtrKey  round keys and J0
 // items and keys are one upload.  [keys, total) is the key region: the last
 // operation a call enqueues overwrites it with zeros.
@@ -26,13 +26,13 @@
 namespace chip {
 namespace cread {
 
+using rules::ENV_OVERHEAD;  // eph_pub65 || nonce16 || tag16 in front of the ciphertext
 using rules::ranges_overlap;
 using rules::up16;
 
 constexpr uint64_t MAX_ITEMS = uint64_t(1) << 31;
 constexpr uint64_t MAX_WORK = uint64_t(1) << 31;
 constexpr uint64_t MAX_OFF = uint64_t(1) << 53;
-constexpr uint64_t ENV_OVERHEAD = 97;  // eph_pub65 || nonce16 || tag16 in front of the ciphertext
 constexpr uint64_t HDR_LEN = 81;       // eph_pub65 || nonce16
 constexpr uint64_t HDR_PITCH = 96;     // a header's slot in the scratch
 
@@ -47,7 +47,7 @@ inline Layout layout(uint64_t nkeys, uint64_t nitems) {
     Layout l;
     l.items = 0;
     l.keys = up16(nitems * sizeof(Item));
-    l.km = l.keys + nkeys * 48;
+    l.km = l.keys + nkeys * RAW_KEY;
     l.total = l.km + nkeys * sizeof(CtrKey);
     return l;
 }
@@ -110,8 +110,8 @@ inline int plan_ctr(const uint8_t *keys, const uint8_t *ivs, uint64_t nkeys, con
             uint32_t &s = slot[item_key[i]];
             if (s == ~uint32_t(0)) {
                 s = used++;
-                std::memcpy(p->table.data() + p->lay.keys + uint64_t(s) * 48, keys + 32ull * item_key[i], 32);
-                std::memcpy(p->table.data() + p->lay.keys + uint64_t(s) * 48 + 32, ivs + 16ull * item_key[i], 16);
+                std::memcpy(p->table.data() + p->lay.keys + uint64_t(s) * RAW_KEY, keys + 32ull * item_key[i], 32);
+                std::memcpy(p->table.data() + p->lay.keys + uint64_t(s) * RAW_KEY + 32, ivs + 16ull * item_key[i], 16);
             }
             it.key = s;
         }

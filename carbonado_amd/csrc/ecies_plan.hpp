@@ -37,7 +37,7 @@ constexpr uint64_t MAX_MSG = (uint64_t(1) << 36) - 32;  // GCM's limit on one me
 constexpr uint64_t MAX_ITEMS = uint64_t(1) << 31;
 constexpr uint64_t HDR_LEN = 81;    // eph_pub65 || nonce16 of an envelope
 constexpr uint64_t HDR_PITCH = 96;  // its slot in the scratch
-constexpr uint64_t ENV_OVERHEAD = 97;  // ... || tag16
+using rules::ENV_OVERHEAD;          // ... || tag16
 
 struct Layout {
     uint64_t msgs = 0, hdrs = 0, keys = 0, km = 0, vals = 0, ok = 0, total = 0;

@@ -1,7 +1,9 @@
 // fread_kernels.hip — KF: the frame index of resident level-14 / level-15
 // streams and the block decode of a ranged read.  The header parse, the walk,
 // the chain check and the sub-range store are in fread_device.hpp (shared with
-// the host check); the block decoder and the CRC are KZ's (snap_device.hpp,
+// the host check); the decode of one frame and the finish of one request are in
+// fread_block.hpp (shared with KG, whose kernels build the work item from the
+// request); the block decoder and the CRC are KZ's (snap_device.hpp,
 // snap_wave.hpp); the keystream of a hop is KC's (cread_device.hpp).  This file
 // maps lanes and waves to streams and work items.
 //
@@ -15,7 +17,7 @@
 #include "fread_kernels.hpp"
 
 #include "bao_device.hpp"
-#include "snap_wave.hpp"
+#include "fread_block.hpp"
 
 namespace chip {
 namespace {
@@ -110,59 +112,15 @@ __global__ __launch_bounds__(64) void fread_block_kernel(FrameLaunch L) {
     // the read failed: the finish kernel zeroes the range.  bad[g] stays unwritten: fread_finish_kernel
     // looks at a request's bad words only where its status word is still 0, and then every one was written
     if (L.status[sg.req] != 0) return;
-    const uint8_t *h = L.rows + sg.src;
-    bool ok = sg.clen >= 4;  // else the index leaves no room for a chunk here: nothing of the row is this frame's
-    uint32_t ty = 0, want = 0;
-    if (ok) {
-        ty = h[0];
-        const uint32_t clen = uint32_t(h[1]) | uint32_t(h[2]) << 8 | uint32_t(h[3]) << 16;
-        want = snap::load32(h + 4);
-        ok = ty <= 1 && clen == sg.clen;
-    }
-    ty = __builtin_amdgcn_readfirstlane(ty);
-    ok = __builtin_amdgcn_readfirstlane(ok ? 1u : 0u) != 0;
-    const uint32_t dl = sg.clen - 4;
-    const uint8_t *from = stage;
-    if (ok && ty == 1) {
-        ok = dl == sg.ulen;
-        from = h + 8;
-    } else if (ok) {
-        snap::Wave w{lane};
-        size_t got = 0;
-        ok = snap::decode_block(w, h + 8, dl, stage, sg.ulen, &got) && got == sg.ulen;
-    }
-    snap::crc_table_fill(tab, lane);
-    __syncthreads();
-    if (ok) ok = snap::wave_crc(tab, from, sg.ulen, lane) == want;
-    if (ok) lane_store(L.content + sg.dst, from + sg.lo, sg.hi - sg.lo, lane);
+    const bool ok = frame_block(sg, L.rows, L.content, stage, tab, lane);
     if (lane == 0) L.bad[g] = ok ? 0u : 1u;
 }
 
 __global__ __launch_bounds__(256) void fread_finish_kernel(FrameLaunch L) {
-    __shared__ uint32_t any;
-    const uint32_t r = blockIdx.x, tid = threadIdx.x;
+    const uint32_t r = blockIdx.x;
     const Req q = L.reqs[r];
-    if (!q.kill && q.n == 0) {  // nothing was asked of the stream: an empty request is served
-        if (tid == 0) L.status[r] = 0;
-        return;
-    }
-    uint32_t st = q.kill ? q.kill : L.status[r];
-    if (tid == 0) any = 0;
-    __syncthreads();
-    if (st == 0)
-        for (uint32_t k = tid; k < q.nseg; k += 256)
-            if (L.bad[q.seg0 + k]) any = 1;
-    __syncthreads();
-    if (st == 0 && any) st = ST_SNAP;
-    if (st == 0) return;
-    lane_zero(L.content + q.dst, q.n, tid, 256);  // no byte of a failed request stays
-    if (tid == 0) {
-        L.status[r] = st;
-        if (q.kill) {
-            L.used[r] = 0;
-            L.vouch[r] = 0;
-        }
-    }
+    finish_request(q.kill, q.n, L.bad + q.seg0, q.nseg, L.content + q.dst, L.status, L.used, L.vouch, r,
+                   threadIdx.x);
 }
 
 }  // namespace

@@ -55,7 +55,7 @@ struct IndexLayout {
     uint64_t out_len = 0;  // of [ostat, oplain end)
     IndexLayout(uint64_t ns, uint64_t ne) {
         rawkeys = up16(ns * sizeof(WStream));
-        km = rawkeys + ns * 48;
+        km = rawkeys + ns * cread::RAW_KEY;
         wout = km + ns * sizeof(cread::CtrKey);
         woff = wout + up16(ns * sizeof(WalkOut));
         vtab = woff + up16(ne * 8);

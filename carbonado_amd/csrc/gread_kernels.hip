@@ -14,13 +14,15 @@
 //    f0 + w / nreq.  It leaves at once where the request's status word is not 0
 //    or the frame is past the request's last; else it builds its fread::Seg in
 //    registers from the request and the frame table (no item table, no search)
-//    and runs the block decode of gread_block.hpp, KF's text: header against
-//    the index, snap::decode_block into 64 KiB of LDS, wave_crc, lane_store of
-//    the wanted bytes, a verdict word;
-//  * gread_finish_kernel: one workgroup per request, what KF's finish kernel
-//    does from the request instead of a table: the verdict words combined,
-//    zeros and status 16, the read's status or the kill status where needed,
-//    and the content length of every request.
+//    and calls fread::frame_block (fread_block.hpp), the one block decode KF's
+//    fread_block_kernel calls too: header against the index,
+//    snap::decode_block into 64 KiB of LDS, wave_crc, lane_store of the wanted
+//    bytes; then its verdict word;
+//  * gread_finish_kernel: one workgroup per request.  It decides the request,
+//    leaves where it was refused, stores the content length of every other
+//    request and calls fread::finish_request (fread_block.hpp), the one finish
+//    KF's fread_finish_kernel feeds from its table: the verdict words combined,
+//    zeros and status 16, the read's status or the kill status where needed.
 //
 // No address and no branch here depends on a secret: requests, frame records,
 // entries, status and key_status words are public, and the staged bytes a
@@ -29,7 +31,7 @@
 // words.
 #include "gread_kernels.hpp"
 
-#include "gread_block.hpp"
+#include "fread_block.hpp"
 
 namespace chip {
 namespace {
@@ -64,12 +66,11 @@ __global__ __launch_bounds__(64) void gread_block_kernel(GreadLaunch L) {
     const Decision d = decide_request(L, r);
     if (d.order != READ || k >= d.nfr) return;
     const fread::Seg sg = item_of_request(L.frecs[d.q_stream], L.ent, d, r, k, L.stage_stride, L.stride);
-    const bool ok = frame_block(sg, L.stage, L.content, stage, tab, lane);
+    const bool ok = fread::frame_block(sg, L.stage, L.content, stage, tab, lane);
     if (lane == 0) L.bad[(uint64_t)r * L.shape.fcap + k] = ok ? 0u : 1u;
 }
 
 __global__ __launch_bounds__(256) void gread_finish_kernel(GreadLaunch L) {
-    __shared__ uint32_t any;
     const uint32_t r = blockIdx.x, tid = threadIdx.x;
     const Decision d = decide_request(L, r);
     if (d.order == REFUSED) {  // the inner planner wrote its words
@@ -78,27 +79,8 @@ __global__ __launch_bounds__(256) void gread_finish_kernel(GreadLaunch L) {
     }
     if (tid == 0) L.content_len[r] = d.n;
     const uint32_t kill = d.order == KILLED ? d.kill : L.key_status ? L.key_status[d.q_stream] : 0u;
-    if (!kill && d.n == 0) {  // nothing was asked of the stream: an empty request is served
-        if (tid == 0) L.status[r] = 0;
-        return;
-    }
-    uint32_t st = kill ? kill : L.status[r];
-    if (tid == 0) any = 0;
-    __syncthreads();
-    if (st == 0)
-        for (uint32_t k = tid; k < d.nfr; k += 256)
-            if (L.bad[(uint64_t)r * L.shape.fcap + k]) any = 1;
-    __syncthreads();
-    if (st == 0 && any) st = fread::ST_SNAP;
-    if (st == 0) return;
-    fread::lane_zero(L.content + (uint64_t)r * L.stride, d.n, tid, 256);  // no byte of a failed request stays
-    if (tid == 0) {
-        L.status[r] = st;
-        if (kill) {
-            L.used[r] = 0;
-            L.vouch[r] = 0;
-        }
-    }
+    fread::finish_request(kill, d.n, L.bad + (uint64_t)r * L.shape.fcap, d.nfr, L.content + (uint64_t)r * L.stride,
+                          L.status, L.used, L.vouch, r, tid);
 }
 
 }  // namespace

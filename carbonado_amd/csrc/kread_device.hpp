@@ -14,11 +14,12 @@
 
 #include "cread_device.hpp"
 #include "qread_device.hpp"
+#include "stream_rules.hpp"
 
 namespace chip {
 namespace kread {
 
-constexpr uint64_t ENV_OVERHEAD = 97;          // eph_pub65 || nonce16 || tag16 in front of the ciphertext
+using rules::ENV_OVERHEAD;                     // eph_pub65 || nonce16 || tag16 in front of the ciphertext
 constexpr uint32_t NO_STREAM = ~uint32_t(0);   // a stream index KQ's planner refuses: nstreams < 2^32
 
 constexpr uint32_t REFUSED = 1;  // order 1 of the header: CHIP_ERR_INVALID_ARG, nothing read

@@ -16,7 +16,8 @@
 //    functions of cread_device.hpp exactly as KC's ctr_range_kernel does,
 //    the neighbour's block through a lane shuffle.  A wave past its request's
 //    content, or whose request's status word is not 0, leaves at once.  The
-//    waves of a killed request store its zeros, span 0 its result words;
+//    waves of a killed request store its zeros, span 0 its result words
+//    (cread::lane_kill, as KC) and its content length;
 //  * kread_table_finish_kernel, behind KC's ctr_setup_kernel when a key table
 //    is made: zeros over the raw key records, and over the record of every
 //    stream whose key_status is not 0.
@@ -53,13 +54,8 @@ __global__ __launch_bounds__(256) void kread_ctr_kernel(KreadLaunch L) {
         const Decision d = decide(L.recs, L.key_status, L.shape, L.req_stream[r], L.start[r], L.len[r]);
         const cread::Item it = item_of_request(r, L.stride, L.start[r], d.clen, s, kill);
         if (span >= cread::work_of(it.n, kill)) return;
-        if (span == 0 && lane == 0) {
-            L.status[r] = kill;
-            L.used[r] = 0;
-            L.vouch[r] = 0;
-            L.content_len[r] = it.n;
-        }
-        cread::lane_zero(it, span, lane, buf);
+        if (span == 0 && lane == 0) L.content_len[r] = it.n;
+        cread::lane_kill(it, span, lane, buf, L.status, L.used, L.vouch, r);
         return;
     }
     const cread::Item it = item_of_request(r, L.stride, L.start[r], L.content_len[r], s, 0);
@@ -76,7 +72,7 @@ __global__ __launch_bounds__(256) void kread_table_finish_kernel(cread::CtrKey *
                                                                  uint8_t *raw, uint32_t nstreams) {
     const uint32_t s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (s >= nstreams) return;
-    if (lane < RAW_KEY / 4) reinterpret_cast<uint32_t *>(raw + RAW_KEY * s)[lane] = 0;
+    if (lane < cread::RAW_KEY / 4) reinterpret_cast<uint32_t *>(raw + cread::RAW_KEY * s)[lane] = 0;
     uint32_t *rec = reinterpret_cast<uint32_t *>(km + s);
     if (key_status[s] != 0) {
         for (uint32_t i = lane; i < sizeof(cread::CtrKey) / 4; i += 64) rec[i] = 0;

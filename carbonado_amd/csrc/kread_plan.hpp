@@ -17,9 +17,6 @@ namespace kread {
 
 using read::up;
 
-static_assert(ENV_OVERHEAD == cread::ENV_OVERHEAD, "one envelope");
-constexpr uint64_t RAW_KEY = 48;  // key (32) || IV (16), as ctr_setup_kernel reads a record
-
 // ---- the key table -----------------------------------------------------------------
 // [nstreams cread::CtrKey | nstreams key_status words | nstreams raw records],
 // every region 16-B aligned.  The words and the raw records are one upload; the
@@ -30,7 +27,7 @@ struct TableLayout {
     explicit TableLayout(uint64_t nstreams) {
         status = nstreams * sizeof(cread::CtrKey);
         raw = status + cread::up16(nstreams * 4);
-        total = raw + nstreams * RAW_KEY;
+        total = raw + nstreams * cread::RAW_KEY;
     }
     uint64_t upload_len() const { return total - status; }
 };
@@ -61,8 +58,8 @@ inline std::vector<uint8_t> table_upload(const uint8_t *keys, const uint8_t *ivs
         const uint32_t ks = key_status ? key_status[s] : 0;
         std::memcpy(t.data() + 4 * s, &ks, 4);
         if (ks) continue;
-        std::memcpy(raw + RAW_KEY * s, keys + 32 * s, 32);
-        std::memcpy(raw + RAW_KEY * s + 32, ivs + 16 * s, 16);
+        std::memcpy(raw + cread::RAW_KEY * s, keys + 32 * s, 32);
+        std::memcpy(raw + cread::RAW_KEY * s + 32, ivs + 16 * s, 16);
     }
     return t;
 }

@@ -23,10 +23,10 @@
 //    audit::chunk_ok; whole quads leave, there is no workgroup barrier;
 //  * paudit_content_kernel: behind the verdicts in stream order, 16 B per
 //    lane over nreq x 64 W units: the verified content of a request whose
-//    status stayed 0, zeros otherwise;
+//    status stayed 0, zeros otherwise (audit::content_unit, as KA);
 //  * paudit_extract_kernel: the proof gather over nreq x (1 + 4 P + 64 W)
-//    units, the text of audit_extract_kernel with the request's own parent
-//    count.
+//    units, a unit past the request's own counts leaving: the header, 16 B of
+//    a parent, 16 B of a chunk (audit::proof_*, as KA).
 //
 // PROOF = false reads a node at its stream offset, PROOF = true at its
 // position in the request's packed pre-order, as in KA.  A lane writes only
@@ -92,16 +92,7 @@ __global__ __launch_bounds__(TPB) void paudit_content_kernel(const Req *reqs, ui
     const Req a = reqs[it.r];
     const uint64_t o = 1024 * it.slot + UNIT * it.unit;  // content bytes [o, o + 16) of the request
     if (o >= a.olen) return;
-    const uint64_t left = a.olen - o;
-    uint8_t *dst = reinterpret_cast<uint8_t *>(a.dst) + o;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (status[it.r] == 0) {  // content starts at the first selected chunk; 16 | 1024: a unit sits in one chunk
-        const uint8_t *p = reinterpret_cast<const uint8_t *>(a.src) +
-                           audit::node_off<PROOF>(a.first + it.slot, 0, a.N, a.first, a.last) + UNIT * it.unit;
-        v = left >= 16 ? load16_a8(p) : load16_partial(p, (uint32_t)left);
-    }
-    if (left >= 16) *glb(reinterpret_cast<u32x4 *>(dst)) = v;
-    else store16_partial(dst, v, (uint32_t)left);
+    audit::content_unit<PROOF>(a, o, status[it.r]);
 }
 
 __global__ __launch_bounds__(TPB) void paudit_extract_kernel(const Req *reqs, const uint64_t *parents, uint32_t nreq,
@@ -111,31 +102,19 @@ __global__ __launch_bounds__(TPB) void paudit_extract_kernel(const Req *reqs, co
     if (i < nreq) {  // the length header, as stored
         const Req a = reqs[i];
         if (a.last == a.first) return;  // refused or spare
-        *glb(reinterpret_cast<uint64_t *>(a.dst)) = *reinterpret_cast<const uint64_t *>(a.src);
-        return;
+        return audit::proof_header(a);
     }
     i -= nreq;
     if (i < 4 * P * nreq) {  // 16 B of a parent
         const Item it = item_of(i, nreq, 4);
         if (it.slot >= parents[it.r]) return;
-        const Req a = reqs[it.r];
-        uint64_t s = 0;
-        const int lv = audit::parent_item(a.N, a.first, a.last, it.slot, &s);
-        const uint64_t w = 16 * it.unit;
-        store16_a8<false>(reinterpret_cast<uint8_t *>(a.dst) + audit::proof_off(s, lv, a.N, a.first, a.last) + w,
-                          load16_a8(reinterpret_cast<const uint8_t *>(a.src) + audit::stream_off(s, lv, a.N) + w));
-        return;
+        return audit::proof_parent_unit(reqs[it.r], it.slot, it.unit);
     }
     i -= 4 * P * nreq;
     const Item it = item_of(i, nreq, 64);
     const Req a = reqs[it.r];
     if (it.slot >= a.last - a.first) return;
-    const uint64_t c = a.first + it.slot, w = 16 * it.unit, clen = audit::chunk_len(c, a.n);
-    if (w >= clen) return;  // past a short last chunk
-    const uint8_t *p = reinterpret_cast<const uint8_t *>(a.src) + audit::stream_off(c, 0, a.N) + w;
-    uint8_t *d = reinterpret_cast<uint8_t *>(a.dst) + audit::proof_off(c, 0, a.N, a.first, a.last) + w;
-    if (w + 16 <= clen) store16_a8<false>(d, load16_a8(p));
-    else store16_partial(d, load16_partial(p, (uint32_t)(clen - w)), (uint32_t)(clen - w));
+    audit::proof_chunk_unit(a, it.slot, it.unit);
 }
 
 // a grid of at least one workgroup: the number of launches of a call is fixed

@@ -191,7 +191,7 @@ inline int plan_unsnap(uintptr_t d_in, const uint64_t *in_off, const uint64_t *i
 inline bool snap_format(uint8_t f) {
     return f < 16 && (f & CHIP_FORMAT_SNAPPY) && (f & (CHIP_FORMAT_BAO | CHIP_FORMAT_ZFEC));
 }
-constexpr uint64_t ENV_OVERHEAD = 97;                  // the Ecies envelope around a frame stream
+using rules::ENV_OVERHEAD;                             // the Ecies envelope around a frame stream
 constexpr uint64_t MAX_STAGE = uint64_t(16) << 20;     // what enters zfec / bao, per object
 
 // what enters zfec / bao at worst for an n-byte object

@@ -21,6 +21,9 @@
 namespace chip {
 namespace rules {
 
+// ---- an Ecies envelope -----------------------------------------------------------
+constexpr uint64_t ENV_OVERHEAD = 97;  // eph_pub65 || nonce16 || tag16 in front of the ciphertext
+
 // ---- a bao stream of n content bytes ------------------------------------------
 RULES_HD uint64_t chunks(uint64_t n) { return n == 0 ? 1 : (n + 1023) / 1024; }
 inline uint64_t bao_len(uint64_t n) { return 8 + n + 64 * (chunks(n) - 1); }

@@ -113,6 +113,7 @@ static void walk(const Call &c, uint8_t *buf, uint64_t buf_len) {
         gcm::aes256_expand(raw, w, km[k].rk);
         setup_lite(km[k].rk, raw + 32, km[k].j0);
     }
+    std::vector<uint32_t> status(nitems, 0xC5C5C5C5u), used(status), vouch(status);  // the result words, canaries
     for (uint64_t w = 0; w < p.work; ++w) {  // the range kernel, one wave per work item
         const uint32_t i = item_of(items, uint32_t(nitems), uint32_t(w));
         const Item it = items[i];
@@ -121,7 +122,8 @@ static void walk(const Call &c, uint8_t *buf, uint64_t buf_len) {
         CHECK(it.buf_off + it.n <= buf_len);
         uint8_t *b = buf + it.buf_off;
         if (it.kill) {
-            for (uint32_t l = 0; l < LANES; ++l) lane_zero(it, span, l, b);
+            for (uint32_t l = 0; l < LANES; ++l)
+                lane_kill(it, span, l, b, status.data(), used.data(), vouch.data(), i);
             continue;
         }
         uint32_t ka[LANES + 1][4], kb[LANES][4];
@@ -131,6 +133,10 @@ static void walk(const Call &c, uint8_t *buf, uint64_t buf_len) {
         }
         for (int j = 0; j < 4; ++j) ka[LANES][j] = 0xDEADBEEFu;  // what lane 63's shuffle reads is not defined
         for (uint32_t l = 0; l < LANES; ++l) lane_apply(it, span, l, ka[l], kb[l], ka[l + 1], b);
+    }
+    for (uint64_t i = 0; i < nitems; ++i) {  // a killed item's words are its status and zeros, a live one's untouched
+        const uint32_t k = items[i].kill;
+        CHECK(status[i] == (k ? k : 0xC5C5C5C5u) && used[i] == (k ? 0u : 0xC5C5C5C5u) && vouch[i] == used[i]);
     }
 }
 
