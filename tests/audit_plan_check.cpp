@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../carbonado_amd/csrc/audit_plan.hpp"
+#include "plan_shift.hpp"
 
 using namespace chip::audit;
 
@@ -217,6 +218,40 @@ static int plan_mode(unsigned seed) {
                        (p == &x ? extract_units(sel.parents, sel.last - sel.first) : (sel.olen + 15) / 16));
                 EXPECT(q.src % 8 == 0 && q.dst % (p == &x ? 8 : 16) == 0);
             }
+        }
+        // the shift case: stream, proof and content offsets moved by D, and the three bases moved by D
+        for (const uint64_t D : plan_shift::SHIFTS) {
+            const std::vector<uint64_t> in_far = plan_shift::moved(in_off, D), po_far = plan_shift::moved(po, D),
+                                        co_far = plan_shift::moved(co, D);
+            std::vector<uint64_t> la(nreq), lb(nreq);
+            Plan xo, xb, vo, vb, wo, wb;
+            EXPECT(plan_extract(STREAMS, in_far.data(), in_len.data(), nstreams, rs.data(), index.data(), count.data(),
+                                nreq, PROOFS, po_far.data(), pl.data(), &xo) == CHIP_OK);
+            EXPECT(plan_extract(STREAMS + D, in_off.data(), in_len.data(), nstreams, rs.data(), index.data(), count.data(),
+                                nreq, PROOFS + D, po.data(), pl.data(), &xb) == CHIP_OK);
+            EXPECT(plan_verify(false, STREAMS, in_far.data(), in_len.data(), nstreams, rs.data(), nullptr, HASH,
+                               index.data(), count.data(), nreq, CONTENT, co_far.data(), la.data(), true, &vo) == CHIP_OK);
+            EXPECT(plan_verify(false, STREAMS + D, in_off.data(), in_len.data(), nstreams, rs.data(), nullptr, HASH,
+                               index.data(), count.data(), nreq, CONTENT + D, co.data(), lb.data(), true, &vb) == CHIP_OK);
+            EXPECT(la == clo && lb == clo);
+            EXPECT(plan_verify(true, PROOFS, po_far.data(), pl.data(), nreq, nullptr, cl.data(), HASH, index.data(),
+                               count.data(), nreq, CONTENT, co_far.data(), la.data(), true, &wo) == CHIP_OK);
+            EXPECT(plan_verify(true, PROOFS + D, po.data(), pl.data(), nreq, nullptr, cl.data(), HASH, index.data(),
+                               count.data(), nreq, CONTENT + D, co.data(), lb.data(), true, &wb) == CHIP_OK);
+            EXPECT(la == clo && lb == clo);
+            Plan *first[3] = {&x, &v, &w}, *by_off[3] = {&xo, &vo, &wo}, *by_base[3] = {&xb, &vb, &wb};
+            for (int k = 0; k < 3; ++k) {
+                EXPECT(by_off[k]->table == by_base[k]->table);
+                EXPECT(by_off[k]->total_parents == first[k]->total_parents && by_off[k]->total_chunks == first[k]->total_chunks &&
+                       by_off[k]->total_units == first[k]->total_units);
+                // per request: where it reads and where it writes, D higher; nothing else changed
+                EXPECT(plan_shift::shifted_words(first[k]->table, by_off[k]->table, D) == (long)(2 * nreq));
+                for (uint64_t r = 0; r < nreq; ++r) {
+                    const Req &q = first[k]->reqs()[r], &f = by_off[k]->reqs()[r];
+                    EXPECT(f.src == q.src + D && f.dst == q.dst + D && f.hash == q.hash);
+                }
+            }
+            EXPECT(!ranges_overlap(po_far.data(), pl.data(), nreq) && !ranges_overlap(co_far.data(), clo.data(), nreq));
         }
         // one thing wrong at a time
         const uint64_t a = rng() % nreq;

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../carbonado_amd/csrc/fread_plan.hpp"
+#include "plan_shift.hpp"
 
 using namespace chip;
 
@@ -155,6 +156,24 @@ static void check_read(std::mt19937_64 &g, uint8_t format) {
     CHECK(stage == p.stage_total && nseg == p.nseg && vseg == p.vseg, "totals");
     for (int n : stored) CHECK(n <= 1, "a content byte stored twice");
     CHECK(!rules::ranges_overlap(p.vcoff.data(), p.vlen.data(), nreq), "rows apart");
+    // the shift case: the plan takes the caller's content offsets and no base (the call adds that on the device);
+    // with every offset D higher, every request's and every segment's destination is D higher, nothing else changed
+    for (const uint64_t D : plan_shift::SHIFTS) {
+        const std::vector<uint64_t> far = plan_shift::moved(coff, D);
+        fread::ReadPlan q;
+        fread::plan_ranges(c.chunk_len.data(), c.padding.data(), c.frame_off.data(), c.idx_off.data(), c.plain_len.data(), kp,
+                           c.shift, rs.data(), start.data(), len.data(), nreq, &q);
+        fread::plan_items(c.frame_off.data(), c.idx_off.data(), c.nframes.data(), c.plain_len.data(), kp, rs.data(),
+                          far.data(), &q);
+        CHECK(q.nseg == p.nseg && q.stage_total == p.stage_total && q.vseg == p.vseg && q.vcoff == p.vcoff, "shifted totals");
+        CHECK(plan_shift::shifted_words(p.table, q.table, D) == (long)(nreq + p.nseg), "shifted table");
+        const fread::Req *qr = reinterpret_cast<const fread::Req *>(q.table.data());
+        const fread::Seg *qs = reinterpret_cast<const fread::Seg *>(q.table.data() + nreq * sizeof(fread::Req));
+        for (uint64_t r = 0; r < nreq; ++r) CHECK(qr[r].dst == reqs[r].dst + D, "shifted request");
+        for (uint64_t k = 0; k < p.nseg; ++k) CHECK(qs[k].dst == segs[k].dst + D && qs[k].src == segs[k].src, "shifted segment");
+        CHECK(rules::ranges_overlap(far.data(), clen.data(), nreq) == rules::ranges_overlap(coff.data(), clen.data(), nreq),
+              "overlap verdict");
+    }
 }
 
 static void check_verify(std::mt19937_64 &g, uint8_t format) {

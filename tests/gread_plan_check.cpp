@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../carbonado_amd/csrc/gread_plan.hpp"
+#include "plan_shift.hpp"
 
 using namespace chip;
 
@@ -334,6 +335,19 @@ static void check_call(std::mt19937_64 &rng) {
         ok.keytab_len = klen;
         ok.scratch_len = need;
         EXPECT(need && need % 16 == 0 && rc(ok, fi) == CHIP_OK && lay.total == need);
+        // the shift case: the frame table holds offsets into frame streams and no address, and the stream table is
+        // qread's (tests/qread_plan_check.cpp); what a call takes is the content base and stride, past 2^32 here
+        for (const uint64_t D : plan_shift::SHIFTS) {
+            A far = ok;
+            far.content = OUT + D;
+            EXPECT(rc(far, fi) == CHIP_OK && lay.total == need);
+            far = ok;
+            far.stride = D + 256;
+            EXPECT(rc(far, fi) == CHIP_OK && lay.total == need);
+            far.stride = D + 264;  // no multiple of 16, at any height
+            EXPECT(rc(far, fi) == CHIP_ERR_INVALID_ARG);
+        }
+        EXPECT(rc(ok, fi) == CHIP_OK && lay.total == need);
         // the layout: the inner scratch first, every region on a 256-B boundary, one after another
         const uint64_t inner = keyed ? kread::scratch_len(&w.info, nreq, g.inner_len)
                                      : qread::scratch_len(&w.info, nreq, g.inner_len, true);

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../carbonado_amd/csrc/kread_plan.hpp"
+#include "plan_shift.hpp"
 
 using namespace chip;
 
@@ -356,6 +357,15 @@ static void check_host() {
     EXPECT(call(0, nullptr, 0, 0, false, 0, 0, 0, 0, false, 9, 0, 0) == CHIP_OK);
     EXPECT(call(TAB, &info, KEYS, tlen, true, 10, 4096, OUT, 4096, true, 1, SCR, need) == CHIP_OK);
     EXPECT(lay.total == need && g.cap == 3);
+    // the shift case: the key table holds no address and the stream table is qread's (tests/qread_plan_check.cpp);
+    // what a call takes is the content base and stride, past 2^32 here: the same verdict, geometry and scratch
+    for (const uint64_t D : plan_shift::SHIFTS) {
+        EXPECT(call(TAB, &info, KEYS, tlen, true, 10, 4096, OUT + D, 4096, true, 1, SCR, need) == CHIP_OK);
+        EXPECT(lay.total == need && g.cap == 3);
+        EXPECT(call(TAB, &info, KEYS, tlen, true, 10, 4096, OUT, D + 256, true, 1, SCR, need) == CHIP_OK);
+        EXPECT(lay.total == need && g.cap == 3);
+        EXPECT(call(TAB, &info, KEYS, tlen, true, 10, 4096, OUT + D, D + 264, true, 1, SCR, need) == CHIP_ERR_INVALID_ARG);
+    }
     EXPECT(call(0, &info, KEYS, tlen, true, 10, 4096, OUT, 4096, true, 0, SCR, need) == CHIP_ERR_INVALID_ARG);
     EXPECT(call(TAB, nullptr, KEYS, tlen, true, 10, 4096, OUT, 4096, true, 0, SCR, need) == CHIP_ERR_INVALID_ARG);
     EXPECT(call(TAB, &info, 0, tlen, true, 10, 4096, OUT, 4096, true, 0, SCR, need) == CHIP_ERR_INVALID_ARG);

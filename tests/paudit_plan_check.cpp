@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../carbonado_amd/csrc/paudit_plan.hpp"
+#include "plan_shift.hpp"
 
 using namespace chip;
 
@@ -147,6 +148,30 @@ int main(int argc, char **argv) {
     for (uint64_t s = 0; s < NS; ++s) {
         EXPECT(roots[s].src == 0 && roots[s].n == recs[s].n && roots[s].N == recs[s].N && roots[s].hash == recs[s].hash);
         EXPECT(recs[s].src == IN + in_off[s] && recs[s].n == SIZES[s] && recs[s].hash == HASH + 32 * s);
+    }
+    // the shift case of the holder's table as the audit kernels read it: stream offsets moved by D, and the base
+    // moved by D; the auditor's root table holds no stream address and takes neither
+    for (const uint64_t D : plan_shift::SHIFTS) {
+        const std::vector<uint64_t> in_far = plan_shift::moved(in_off, D);
+        chipq_table_info info2, info3;
+        std::vector<uint8_t> by_off, by_base;
+        EXPECT(qread::plan_table(IN, in_far.data(), in_len.data(), HASH, padding.data(), chunk_len.data(), NS, TAB,
+                                 qread::table_len(NS), &info2, &by_off) == CHIP_OK);
+        EXPECT(qread::plan_table(IN + D, in_off.data(), in_len.data(), HASH, padding.data(), chunk_len.data(), NS, TAB,
+                                 qread::table_len(NS), &info3, &by_base) == CHIP_OK);
+        EXPECT(by_off == by_base && info2.max_chunks == info.max_chunks && info3.nstreams == info.nstreams);
+        EXPECT(plan_shift::shifted_words(table, by_off, D) == (long)NS);
+        const paudit::StreamRec *far = reinterpret_cast<const paudit::StreamRec *>(by_off.data());
+        for (uint64_t s = 0; s < NS; ++s)
+            EXPECT(far[s].src == recs[s].src + D && far[s].n == recs[s].n && far[s].N == recs[s].N && far[s].hash == recs[s].hash);
+        // a call whose content and proof slots lie past 2^32, base or pitch: the same geometry and scratch
+        paudit::Geometry g1, g2, g3;
+        paudit::ScratchLayout l1, l2, l3;
+        const uint64_t need = paudit::scratch_len(66, 10, 3), pb = audit::up(paudit::proof_bound(66, 3), 16);
+        EXPECT(paudit::plan_call(true, TAB, 66, 10, 3, true, OUT, 3072, true, PRF, pb, SCR, need, &g1, &l1) == CHIP_OK);
+        EXPECT(paudit::plan_call(true, TAB, 66, 10, 3, true, OUT + D, 3072, true, PRF + D, pb, SCR, need, &g2, &l2) == CHIP_OK);
+        EXPECT(paudit::plan_call(true, TAB, 66, 10, 3, true, OUT, D + 256, true, PRF, D + 256, SCR, need, &g3, &l3) == CHIP_OK);
+        EXPECT(g1.W == g2.W && g1.W == g3.W && l1.total == l2.total && l1.total == l3.total && l1.total == need);
     }
 
     for (int round = 0; round < 60; ++round) {

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../carbonado_amd/csrc/qread_plan.hpp"
+#include "plan_shift.hpp"
 
 using namespace chip;
 
@@ -98,6 +99,29 @@ int main(int argc, char **argv) {
         EXPECT(info.nstreams == nstreams && info.min_shard == 1024 && info.max_chunks >= 8 && info.reserved == 0);
         const qread::StreamRec *recs = reinterpret_cast<const qread::StreamRec *>(table.data());
         EXPECT(recs[4].C == 0);
+        // the shift case: every stream offset moved by D, and the base moved by D: the same table, each record's
+        // stream address D higher, the same info; and a call whose content base and stride lie past 2^32
+        for (const uint64_t D : plan_shift::SHIFTS) {
+            const std::vector<uint64_t> in_far = plan_shift::moved(in_off, D);
+            chipq_table_info info2, info3;
+            std::vector<uint8_t> by_off, by_base;
+            EXPECT(qread::plan_table(IN, in_far.data(), in_len.data(), HASH, padding.data(), chunk_len.data(), nstreams, TAB,
+                                     qread::table_len(nstreams), &info2, &by_off) == CHIP_OK);
+            EXPECT(qread::plan_table(IN + D, in_off.data(), in_len.data(), HASH, padding.data(), chunk_len.data(), nstreams,
+                                     TAB, qread::table_len(nstreams), &info3, &by_base) == CHIP_OK);
+            EXPECT(by_off == by_base && !std::memcmp(&info2, &info, sizeof info) && !std::memcmp(&info3, &info, sizeof info));
+            EXPECT(plan_shift::shifted_words(table, by_off, D) == (long)nstreams);
+            const qread::StreamRec *far = reinterpret_cast<const qread::StreamRec *>(by_off.data());
+            for (uint64_t k = 0; k < nstreams; ++k) EXPECT(far[k].src == recs[k].src + D && far[k].hash == recs[k].hash);
+            qread::Geometry g1, g2;
+            qread::ScratchLayout l1, l2;
+            const uint64_t need = qread::scratch_len(&info, nreq, max_len, true);
+            EXPECT(qread::plan_call(TAB, &info, true, nreq, max_len, OUT, stride, true, true, 0, SCR, need, &g1, &l1) == CHIP_OK);
+            EXPECT(qread::plan_call(TAB, &info, true, nreq, max_len, OUT + D, D + 256, true, true, 0, SCR, need, &g2, &l2) ==
+                   CHIP_OK);
+            EXPECT(g1.ok && g2.ok && g1.S == g2.S && g1.nslot == g2.nslot && g1.blocks == g2.blocks && g1.parents == g2.parents);
+            EXPECT(l1.total == l2.total && l1.total <= need && l1.segs == l2.segs && l1.contra == l2.contra);
+        }
 
         std::vector<uint32_t> rs(nreq);
         std::vector<uint64_t> start(nreq), len(nreq), coff(nreq);

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../carbonado_amd/csrc/ragged_plan.hpp"
+#include "plan_shift.hpp"
 
 using namespace chip::ragged;
 
@@ -75,6 +76,43 @@ int main(int argc, char **argv) {
         EXPECT(dec_len == n);
         check_plan(d, format);
         EXPECT(scratch_len(format, out_len.data(), count, 1) == d.lay.total);
+        // the shift case: every offset moved by D, and the bases moved by D: the same tables, the addresses D higher
+        for (const uint64_t D : plan_shift::SHIFTS) {
+            const std::vector<uint64_t> in_far = plan_shift::moved(in_off, D), out_far = plan_shift::moved(out_off, D);
+            std::vector<uint64_t> len2(count), len3(count);
+            EXPECT(!ranges_overlap(out_far.data(), lay_len.data(), count));
+            for (int decode = 0; decode < 2; ++decode) {
+                Plan &first = decode ? d : p;
+                Plan by_off, by_base;
+                if (decode) {
+                    EXPECT(plan_decode(format, OUT, out_far.data(), out_len.data(), count, pad.data(), IN, in_far.data(),
+                                       len2.data(), &by_off) == CHIP_OK);
+                    EXPECT(plan_decode(format, OUT + D, out_off.data(), out_len.data(), count, pad.data(), IN + D,
+                                       in_off.data(), len3.data(), &by_base) == CHIP_OK);
+                    EXPECT(len2 == n && len3 == n);
+                } else {
+                    EXPECT(plan_encode(format, IN, in_far.data(), n.data(), count, OUT, out_far.data(), len2.data(),
+                                       &by_off) == CHIP_OK);
+                    EXPECT(plan_encode(format, IN + D, in_off.data(), n.data(), count, OUT + D, out_off.data(), len3.data(),
+                                       &by_base) == CHIP_OK);
+                    EXPECT(len2 == lay_len && len3 == lay_len);
+                }
+                EXPECT(by_off.table == by_base.table && by_off.lay.total == first.lay.total);
+                EXPECT(by_off.total_groups == first.total_groups && by_off.total_blocks == first.total_blocks);
+                // per object: two addresses (src and stream, or stream and out) D higher, nothing else changed
+                EXPECT(plan_shift::shifted_words(first.table, by_off.table, D) == (long)(2 * count));
+                for (uint64_t o = 0; o < count; ++o) {
+                    const Obj &a = first.objs()[o], &b = by_off.objs()[o];
+                    EXPECT((uintptr_t)b.stream == (uintptr_t)a.stream + D);
+                    EXPECT((uintptr_t)(decode ? b.out : b.src) == (uintptr_t)(decode ? a.out : a.src) + D);
+                }
+            }
+            if (count >= 2 && out_len[0] && out_len[1]) {  // an overlap is an overlap at any height
+                std::vector<uint64_t> bad = out_far;
+                bad[1] = bad[0];
+                EXPECT(ranges_overlap(bad.data(), out_len.data(), count));
+            }
+        }
         if (count >= 2) {  // two outputs made to share a byte; a misaligned one; an oversize one
             std::vector<uint64_t> bad = out_off;
             const uint64_t a = rng() % count, b = (a + 1) % count;

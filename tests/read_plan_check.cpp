@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../carbonado_amd/csrc/read_plan.hpp"
+#include "plan_shift.hpp"
 
 using namespace chip;
 using namespace chip::read;
@@ -137,6 +138,28 @@ int main(int argc, char **argv) {
             EXPECT(plan_read(IN, in_off.data(), in_len.data(), HASH, padding.data(), chunk_len.data(), nstreams,
                              req_stream.data(), start.data(), len.data(), nreq, OUT, off.data(), clen2.data(), true, SCR,
                              p.lay.total - 1, &q) == CHIP_ERR_INVALID_ARG);
+        }
+        // the shift case: stream and content offsets moved by D, and the two bases moved by D
+        for (const uint64_t D : plan_shift::SHIFTS) {
+            const std::vector<uint64_t> in_far = plan_shift::moved(in_off, D), off_far = plan_shift::moved(off, D);
+            std::vector<uint64_t> len_a(nreq), len_b(nreq);
+            Plan by_off, by_base;
+            EXPECT(plan_read(IN, in_far.data(), in_len.data(), HASH, padding.data(), chunk_len.data(), nstreams,
+                             req_stream.data(), start.data(), len.data(), nreq, OUT, off_far.data(), len_a.data(), true,
+                             SCR, need, &by_off) == CHIP_OK);
+            EXPECT(plan_read(IN + D, in_off.data(), in_len.data(), HASH, padding.data(), chunk_len.data(), nstreams,
+                             req_stream.data(), start.data(), len.data(), nreq, OUT + D, off.data(), len_b.data(), true,
+                             SCR, need, &by_base) == CHIP_OK);
+            EXPECT(len_a == clen2 && len_b == clen2 && by_off.ka.table == by_base.ka.table);
+            EXPECT(by_off.nseg == p.nseg && by_off.total_blocks == p.total_blocks && by_off.fb_parents == p.fb_parents);
+            EXPECT(by_off.prim_parents == p.prim_parents && by_off.prim_chunks == p.prim_chunks);
+            // per segment: the stream's address twice (the segment, its slice request) and the content address
+            EXPECT(plan_shift::shifted_words(p.ka.table, by_off.ka.table, D) == (long)(3 * p.nseg));
+            for (uint64_t k = 0; k < p.nseg; ++k) {
+                EXPECT(by_off.segs()[k].src == p.segs()[k].src + D && by_off.segs()[k].dst == p.segs()[k].dst + D);
+                EXPECT(by_off.ka.reqs()[k].src == p.ka.reqs()[k].src + D && by_off.ka.reqs()[k].hash == p.ka.reqs()[k].hash);
+            }
+            EXPECT(audit::ranges_overlap(off_far.data(), clen2.data(), nreq) == audit::ranges_overlap(off.data(), clen2.data(), nreq));
         }
         uint64_t g = 0;
         const uint64_t *parents = p.ka.parents(), *chunks = p.ka.chunks();

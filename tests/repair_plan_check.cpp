@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../carbonado_amd/csrc/repair_plan.hpp"
+#include "plan_shift.hpp"
 
 using namespace chip;
 using namespace chip::repair;
@@ -200,6 +201,34 @@ int main(int argc, char **argv) {
         EXPECT(ap.total_units == 0 && ap.total_chunks == all_chunks);  // every chunk of a stream in one shard
         expect_disjoint({{V.audit, V.audit + ap.lay.total}, {V.first, V.first + 4 * (count + 1)},
                          {V.rstat, V.rstat + 32 * count}, {V.masks, V.masks + 4 * count}}, V.end);
+        // the shift case of the checks and the verdict requests: offsets moved by D, and the bases moved by D
+        for (const uint64_t D : plan_shift::SHIFTS) {
+            const std::vector<uint64_t> in_far = plan_shift::moved(in_off, D), out_far = plan_shift::moved(out_off, D);
+            std::vector<uint64_t> n2;
+            EXPECT(check_args(true, IN, in_far.data(), in_len.data(), count, HASH, padding.data(), chunk_len.data(), OUT,
+                              out_far.data(), &status_dummy, SCR, one, &n2) == CHIP_OK && n2 == n);
+            EXPECT(check_args(true, IN + D, in_off.data(), in_len.data(), count, HASH, padding.data(), chunk_len.data(),
+                              OUT + D, out_off.data(), &status_dummy, SCR, one, &n2) == CHIP_OK && n2 == n);
+            EXPECT(check_args(true, IN, in_far.data(), in_len.data(), count, HASH, padding.data(), chunk_len.data(), IN,
+                              in_far.data(), &status_dummy, SCR, one, &n2) == CHIP_OK);  // in place, far
+            EXPECT(!bad_overlap(IN, in_far.data(), OUT, out_far.data(), in_len.data(), count));
+            EXPECT(!bad_overlap(IN, in_far.data(), IN, in_far.data(), in_len.data(), count));
+            if (count >= 2) {
+                std::vector<uint64_t> lap = out_far;
+                lap[1] = lap[0] + 8;  // two outputs share bytes
+                EXPECT(bad_overlap(IN, in_far.data(), OUT, lap.data(), in_len.data(), count));
+                EXPECT(bad_overlap(IN + D, in_off.data(), IN, lap.data(), in_len.data(), count) ==
+                       bad_overlap(IN, in_far.data(), IN, lap.data(), in_len.data(), count));
+            }
+            audit::Plan by_off, by_base;
+            std::vector<uint32_t> f2, f3;
+            EXPECT(plan_verdicts(IN, in_far.data(), n, spoiled.data(), HASH, &by_off, &f2) == CHIP_OK);
+            EXPECT(plan_verdicts(IN + D, in_off.data(), n, spoiled.data(), HASH, &by_base, &f3) == CHIP_OK);
+            EXPECT(f2 == first && f3 == first && by_off.table == by_base.table && by_off.total_chunks == ap.total_chunks);
+            EXPECT(plan_shift::shifted_words(ap.table, by_off.table, D) == (long)ap.nreq);  // each request's stream address
+            for (uint64_t r = 0; r < ap.nreq; ++r)
+                EXPECT(by_off.reqs()[r].src == ap.reqs()[r].src + D && by_off.reqs()[r].hash == ap.reqs()[r].hash);
+        }
         // some streams to repair, each with a random 4-subset; packed into passes under several scratch sizes
         std::vector<Repair> reps;
         for (uint64_t o = 0; o < count; ++o) {
@@ -253,6 +282,23 @@ int main(int argc, char **argv) {
                     EXPECT(e.valid == 4 * a.C - r.pad);
                 }
                 expect_disjoint(regs, p.lay.total);
+                // the shift case of a pass: the streams read and the outputs committed D higher, the scratch where it was
+                for (const uint64_t D : plan_shift::SHIFTS) {
+                    const std::vector<uint64_t> in_far = plan_shift::moved(in_off, D), out_far = plan_shift::moved(out_off, D);
+                    Pass by_off, by_base;
+                    EXPECT(plan_pass(reps.data() + range.first, R, SCR + V.end, IN, in_far.data(), OUT, out_far.data(), HASH,
+                                     &by_off) == CHIP_OK);
+                    EXPECT(plan_pass(reps.data() + range.first, R, SCR + V.end, IN + D, in_off.data(), OUT + D, out_off.data(),
+                                     HASH, &by_base) == CHIP_OK);
+                    EXPECT(by_off.table == by_base.table && by_off.enc.table == by_base.enc.table);
+                    EXPECT(by_off.total_blocks == p.total_blocks && by_off.total_units == p.total_units);
+                    EXPECT(by_off.enc.table == p.enc.table);  // the re-encode works inside the scratch
+                    EXPECT(plan_shift::shifted_words(p.table, by_off.table, D) == (long)(2 * R));
+                    for (uint64_t j = 0; j < R; ++j) {
+                        EXPECT(by_off.recs()[j].src == p.recs()[j].src + D && by_off.recs()[j].dst == p.recs()[j].dst);
+                        EXPECT(by_off.commits()[j].out == p.commits()[j].out + D && by_off.commits()[j].row == p.commits()[j].row);
+                    }
+                }
             }
             EXPECT(next == reps.size());
         }

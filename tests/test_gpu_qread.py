@@ -126,14 +126,18 @@ class Planned(RW.Planned):
                                   self.clen, self.status, self.used, self.scratch)
 
 
-def reference(w: World, reqs, max_len, stride, vouched, flags=0) -> Got:
+def reference(w: World, reqs, max_len, stride, vouched, flags=0, content=None, content_base=0) -> Got:
     """The host-planned call over the same requests at r * stride; a refused
-    request reads an empty range there and has status 1, used 0, vouch 0 here."""
+    request reads an empty range there and has status 1, used 0, vouch 0 here.
+    `content`: a canary-filled buffer of the caller's, request r at
+    content_base + r * stride of it (w is then any object with World's fields)."""
     torch, D = w.torch, w.D
     n = len(reqs)
     rs, start, length, coff = RW.host_requests(reqs, stride)
     _, _, _, nseg = D.read_layout(w.cls, w.pads, rs, start, length, 16)
-    content = torch.full((n * stride + 64,), CANARY, dtype=torch.uint8, device="cuda")
+    if content is None:
+        content = torch.full((n * stride + 64,), CANARY, dtype=torch.uint8, device="cuda")
+    coff = [content_base + c for c in coff]
     status = torch.zeros(n, dtype=torch.int32, device="cuda")
     used = torch.zeros(n, dtype=torch.int32, device="cuda")
     vouch = torch.zeros(n, dtype=torch.int32, device="cuda")
@@ -143,7 +147,8 @@ def reference(w: World, reqs, max_len, stride, vouched, flags=0) -> Got:
     else:
         clen = D.read_ranges(w.buf, w.off, w.len, w.hashes, w.pads, w.cls, rs, start, length, content, coff, status, used,
                              D.read_scratch(n, nseg))
-    return RW.host_result(reqs, clen, content, status, used, vouch if vouched else None)
+    return RW.host_result(reqs, clen, content[content_base:content_base + n * stride + 64], status, used,
+                          vouch if vouched else None)
 
 
 def _requests(nreq, max_len):
@@ -151,10 +156,11 @@ def _requests(nreq, max_len):
     return [base[(r + nreq) % len(base)] for r in range(nreq)]
 
 
-def test_base_set_is_what_it_says(gpu):
-    """The reference itself: the clean objects' bytes, and every damage class is there."""
-    w = world()
-    for max_len in (4096, 5000):
+def check_base_set(w, reference, max_lens=(4096, 5000)):
+    """The host-planned calls over the base set: the clean objects' bytes, and
+    every damage class is there.  reference(w, reqs, max_len, stride, vouched
+    [, flags]) is the function above, or it with a content buffer of the caller's."""
+    for max_len in max_lens:
         reqs = base_requests(max_len)
         stride = (max_len + 15) // 16 * 16 + 16
         ref = reference(w, reqs, max_len, stride, True)
@@ -180,6 +186,11 @@ def test_base_set_is_what_it_says(gpu):
         assert ref.status[by[CONTRA, 1024, 100]] == 0
         plain = reference(w, reqs, max_len, stride, False)
         assert plain.status[by[CONTRA, 5, 100]] == 0 and plain.status[by[PARENT, 2058, 100]] == 0
+
+
+def test_base_set_is_what_it_says(gpu):
+    """The reference itself: the clean objects' bytes, and every damage class is there."""
+    check_base_set(world(), reference)
 
 
 # 512: S = 4 slots per request, so 2049 entries per prefix array: three scan workgroups of 1024 entries, and one

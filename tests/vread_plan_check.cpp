@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../carbonado_amd/csrc/vread_plan.hpp"
+#include "plan_shift.hpp"
 
 using namespace chip;
 
@@ -106,6 +107,26 @@ int main(int argc, char **argv) {
             EXPECT(vread::plan_vread(IN, in_off.data(), in_len.data(), HASH, padding.data(), chunk_len.data(), nstreams,
                                      req_stream.data(), start.data(), len.data(), nreq, OUT, off.data(), clen2.data(),
                                      true, flags, SCR, p.lay.total - 1, &r) == CHIP_ERR_INVALID_ARG);
+        }
+        // the shift case: stream and content offsets moved by D, and the two bases moved by D
+        for (const uint64_t D : plan_shift::SHIFTS) {
+            const std::vector<uint64_t> in_far = plan_shift::moved(in_off, D), off_far = plan_shift::moved(off, D);
+            std::vector<uint64_t> len_a(nreq), len_b(nreq);
+            vread::Plan by_off, by_base;
+            EXPECT(vread::plan_vread(IN, in_far.data(), in_len.data(), HASH, padding.data(), chunk_len.data(), nstreams,
+                                     req_stream.data(), start.data(), len.data(), nreq, OUT, off_far.data(), len_a.data(),
+                                     true, flags, SCR, need, &by_off) == CHIP_OK);
+            EXPECT(vread::plan_vread(IN + D, in_off.data(), in_len.data(), HASH, padding.data(), chunk_len.data(), nstreams,
+                                     req_stream.data(), start.data(), len.data(), nreq, OUT + D, off.data(), len_b.data(),
+                                     true, flags, SCR, need, &by_base) == CHIP_OK);
+            EXPECT(len_a == clen2 && len_b == clen2 && by_off.rd.ka.table == by_base.rd.ka.table);
+            EXPECT(by_off.rd.nseg == ns && by_off.vouch_items == p.vouch_items && by_off.lay.total == p.lay.total);
+            EXPECT(by_off.rd.total_blocks == p.rd.total_blocks && by_off.rd.fb_parents == p.rd.fb_parents);
+            EXPECT(plan_shift::shifted_words(p.rd.ka.table, by_off.rd.ka.table, D) == (long)(3 * ns));
+            for (uint64_t k = 0; k < ns; ++k) {
+                EXPECT(by_off.rd.segs()[k].src == p.rd.segs()[k].src + D && by_off.rd.segs()[k].dst == p.rd.segs()[k].dst + D);
+                EXPECT(by_off.rd.ka.reqs()[k].src == p.rd.ka.reqs()[k].src + D);
+            }
         }
         // vouch items: segment g's are its window's chunks, and every item maps back to (segment, chunk) once
         const uint64_t *pre = p.rd.ka.chunks();
